@@ -30,6 +30,12 @@ launcher starts one itself (``python -m torch.distributed.run --nproc-per-node N
 child process, before anything touches the GPU) and passes its output through.
 GTR_SHARE_DEVICE=1 puts every rank on cuda:0 over gloo (a rehearsal on a one-GPU box).
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full``
+adds the legs measured beside the headline (CPU baseline, end-to-end, drop-in trainer,
+gather rooflines, C1, Recall@10 parity, the step-tail probe, the strong-scaling child
+runs); ``--dump-outputs DIR`` writes the last timed step's loss and the trained tensors
+as ``DIR/<name>.npy``.
+
 Prints ONE JSON line (rank 0).
 """
 
@@ -115,6 +121,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps also run the legs beside it: the CPU baseline, the "
+                         "end-to-end, drop-in trainer, gather-roofline, C1 and Recall@10 legs, the step-tail probe "
+                         "and the strong-scaling child runs (each with its own switch below).  Without it a run "
+                         "sets up, warms up, times the steps and prints the line; those fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed -- the last step's loss and every trained "
+                         "tensor of the model's state_dict -- as DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--batch-size", type=int, default=None, help="sessions per GPU (default 32; c5: 8192)")
     ap.add_argument("--num-batches", type=int, default=None,
                     help="distinct pre-staged batches per GPU (default 64, fewer at large batches: about 32k "
@@ -306,6 +320,8 @@ def main():
         elapsed = float(t.item())
     final_loss = float(loss)
     step.sync_table()  # lazy table: rows brought to the last step; sharded: gathered from the shards
+    if args.dump_outputs and rank == 0:  # before any leg that steps the model again (the tail probe)
+        dump_outputs(args.dump_outputs, loss, step.model)
     replicas_identical = None
     if world > 1:  # data parallel: every rank must hold the same parameters
         chk = torch.stack([step.model.item_embedding.weight.double().sum(), step.eng.flat.flat.double().sum()])
@@ -326,35 +342,35 @@ def main():
     achieved = alg_bytes / (step_ms * 1e-3) / 1e9
     traffic, traffic_src = (load_traffic(args.config if B == cfg.get("batch", 32) else f"{args.config}_b{B}",
                                          lazy) if step.dp is None and not shard else (None, None))
-    tail_ms = measure_tail(step, args.steps) if args.tail_probe and not shard else None
+    tail_ms = measure_tail(step, args.steps) if args.full and args.tail_probe and not shard else None
 
     log(f"timed: {value:.1f} sessions/s, {ms_per_step:.4f} ms/step")
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(cfg, batches, T, args.cpu_seconds)
         log(f"cpu baseline: {cpu['value']} sessions/s")
     e2e = None
-    if rank == 0 and world == 1 and args.e2e_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.e2e_steps > 0:
         e2e = e2e_probe(cfg, data, dev, B, args.e2e_steps)
         log(f"end to end: {e2e['device_batch_build_sessions_per_s']} sessions/s")
     trainer_leg = None
-    if rank == 0 and world == 1 and args.trainer_epochs > 0 and not shard:
+    if args.full and rank == 0 and world == 1 and args.trainer_epochs > 0 and not shard:
         trainer_leg = trainer_epoch_probe(cfg, data, dev, B, args.trainer_epochs)
         trainer_leg["vs_headline_ms_per_step"] = round(trainer_leg["ms_per_step"] / ms_per_step, 4)
         log(f"trainer epoch: {trainer_leg['sessions_per_s']} sessions/s, {trainer_leg['ms_per_step']} ms/step")
     gather = gather_c = None
-    if rank == 0 and world == 1 and args.gather_batch > 0:
+    if args.full and rank == 0 and world == 1 and args.gather_batch > 0:
         gather = gather_probe(dev, args.gather_batch, "c5")
         log(f"gather roofline (C5 table): frac {gather['frac']}")
         gather_c = gather_probe(dev, args.gather_batch, "c3")
         log(f"gather roofline (C3 table): frac {gather_c['frac']}")
     c1 = None
-    if rank == 0 and world == 1 and args.c1_reps > 0:
+    if args.full and rank == 0 and world == 1 and args.c1_reps > 0:
         c1 = c1_quick(dev, args.c1_reps)
         log(f"C1 quick validation: HIP {c1['hip_ms_per_3_steps']} ms, CPU oracle {c1['cpu_oracle_ms_per_3_steps']} ms "
             "per 3 steps")
     recall = None
-    if rank == 0 and world == 1 and args.recall_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.recall_steps > 0:
         recall = recall_parity(cfg, data, T, dev, args.recall_steps, args.recall_sessions)
         log(f"recall parity: {recall['gpu']} vs {recall['oracle']}")
 
@@ -455,7 +471,7 @@ def main():
         torn_down = True
     if rank == 0:
         legs = [int(x) for x in args.strong_batches.split(",") if x.strip() and int(x) > 0]
-        if legs and not cfg.get("shard") and os.environ.get("GTR_STRONG_CHILD") != "1":
+        if args.full and legs and not cfg.get("shard") and os.environ.get("GTR_STRONG_CHILD") != "1":
             del w, step, staged
             torch.cuda.empty_cache()
             out["strong_scaling"] = strong_scaling_legs(world, legs, args.strong_steps)
@@ -464,6 +480,35 @@ def main():
     if not torn_down:
         sys.stderr.flush()
         os._exit(0)
+
+
+DUMP_BUDGET = 60 << 20  # bytes of float32 over all dumped arrays (below the 64 MB a dump may take)
+
+
+def dump_outputs(out_dir: str, loss, model) -> None:
+    """What the timed steps computed, as ``out_dir/<name>.npy`` (float32): the last step's
+    loss and every floating-point tensor of the trained model's state_dict (the item table
+    after ``sync_table``, the layer weights, the BatchNorm statistics).  Tensors below
+    1 MB are written whole.  If everything together exceeds DUMP_BUDGET, each larger
+    tensor keeps a fixed sample of its rows: the same share of the remaining budget each,
+    row indices drawn once by ``default_rng(0)`` from the tensor's row count and sorted, so
+    two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    for k, v in model.state_dict().items():
+        if torch.is_floating_point(v):
+            arrays[k] = v.detach().float().cpu().numpy()
+    big = [k for k, a in arrays.items() if a.nbytes >= 1 << 20]
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        share = (DUMP_BUDGET - sum(a.nbytes for k, a in arrays.items() if k not in big)) // len(big)
+        for k in big:
+            a = arrays[k].reshape(arrays[k].shape[0], -1)
+            rows = share // (a.shape[1] * a.itemsize)
+            if rows < a.shape[0]:
+                arrays[k] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB -> {out_dir}")
 
 
 def _bounded(fn, seconds: float) -> bool:

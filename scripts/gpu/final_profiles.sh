@@ -8,7 +8,7 @@ export ROUND=${ROUND:-r06}
 ALL="c2 c3_b8192 c4_b1024_split c4_b1024 c4_b8192 c5 c5_b1024"
 for c in ${@:-$ALL}; do
   case $c in
-    c2) BENCH_ARGS_FULL="--gpus 1 --steps 20 --warmup 5" bash scripts/gpu/profile.sh c2 c2 || exit 1 ;;
+    c2) BENCH_ARGS_FULL="--full --gpus 1 --steps 20 --warmup 5" bash scripts/gpu/profile.sh c2 c2 || exit 1 ;;
     c3_b8192) bash scripts/gpu/profile.sh c3 c3_b8192 --batch-size 8192 || exit 1 ;;
     c4_b1024_split) GTR_SPLIT=1 bash scripts/gpu/profile.sh c4 c4_b1024_split --global-batch 1024 || exit 1 ;;
     c4_b1024) bash scripts/gpu/profile.sh c4 c4_b1024 --global-batch 1024 || exit 1 ;;

@@ -50,8 +50,8 @@ def test_bench_gpus2_launches_two_ranks():
     """The default line at N = 2, with its strong-scaling leg: the C4 mode (row-sharded
     table, SyncBN) at a fixed global batch over the same two ranks, launched as a child
     after the main line's process group is gone."""
-    out = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--num-batches", "4", "--strong-batches", "512",
-                  "--strong-steps", "3"])
+    out = _bench(["--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--num-batches", "4",
+                  "--strong-batches", "512", "--strong-steps", "3"])
     assert out["n_gpus"] == 2
     cfg = out["config"]
     assert cfg["process_group_world"] == 2 and cfg["launcher"].startswith("bench.py --gpus")
@@ -68,12 +68,42 @@ def test_bench_gpus2_launches_two_ranks():
 
 
 def test_bench_one_gpu_strong_leg_reports_the_unsharded_step_beside_it():
-    out = _bench(["--steps", "3", "--warmup", "1", "--num-batches", "2", "--strong-batches", "256",
+    out = _bench(["--full", "--steps", "3", "--warmup", "1", "--num-batches", "2", "--strong-batches", "256",
                   "--strong-steps", "3"])
     leg = out["strong_scaling"]["legs"][0]
     assert "error" not in leg, leg
     assert leg["parallelism"] == "dp1+rowshard" and leg["process_group_world"] is None
     assert leg["unsharded_single_gpu"]["value"] > 0
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` (and with every leg's own switch at its default) the line holds
+    the headline figures and none of the legs; ``--dump-outputs`` writes the last step's
+    loss and the trained tensors as float32, the same arrays on a second run."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--num-batches", "2"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), *args, "--dump-outputs",
+                            str(tmp_path / d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "sessions/s" and out["dtype"] == "fp32"
+        assert abs(out["value"] - 32 * 1e3 / out["ms_per_step"]) <= 0.01 * out["value"]
+        assert out["config"]["step_graph"].startswith("3 consecutive steps")
+        for leg in ("cpu_baseline", "end_to_end", "trainer_epoch", "gather_roofline", "gather_roofline_infinity_cache",
+                    "recall_parity", "c1_quick_validation"):
+            assert out[leg] is None, leg
+        assert "strong_scaling" not in out and out["roofline"]["tail_kernel"]["avg_launch_ms"] is None
+        dumps.append({n: np.load(tmp_path / d / n) for n in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert {"loss.npy", "item_embedding.weight.npy", "convs.0.lin_query.weight.npy"} <= set(a) and set(a) == set(b)
+    assert a["item_embedding.weight.npy"].shape == (82174, 64) and abs(float(a["loss.npy"][0]) - out["config"]["final_loss"]) < 1e-6
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
 
 
 def test_bench_c4_gpus2_sharded_strong():

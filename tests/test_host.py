@@ -472,3 +472,34 @@ def test_bench_step_graph_plan_covers_exactly_k_steps():
                 assert S % nimg == 0 and S <= max(256, nimg)
             else:
                 assert (S, full, rem) == (steps, 1, 0)
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss and every floating-point state_dict tensor as
+    float32 .npy (integer buffers are left out); within the budget whole, above it each
+    tensor of 1 MB or more as the same sorted row sample on every call."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(__file__), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Embedding(5000, 64), torch.nn.BatchNorm1d(64))  # table: 1.28 MB
+    loss = torch.tensor(0.25)
+    bench.dump_outputs(str(tmp_path / "whole"), loss, model)
+    names = sorted(os.listdir(tmp_path / "whole"))
+    assert names == ["0.weight.npy", "1.bias.npy", "1.running_mean.npy", "1.running_var.npy", "1.weight.npy", "loss.npy"]
+    tab = np.load(tmp_path / "whole" / "0.weight.npy")
+    assert tab.dtype == np.float32 and np.array_equal(tab, model[0].weight.detach().numpy())
+    assert np.load(tmp_path / "whole" / "loss.npy").tolist() == [0.25]
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1 << 19)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), loss, model)
+    s1, s2 = np.load(tmp_path / "s1" / "0.weight.npy"), np.load(tmp_path / "s2" / "0.weight.npy")
+    assert np.array_equal(s1, s2) and s1.shape[1] == 64 and 1000 < s1.shape[0] < 5000
+    rows = np.sort(np.random.default_rng(0).choice(5000, size=s1.shape[0], replace=False))
+    assert np.array_equal(s1, tab[rows])
+    assert sum(os.path.getsize(tmp_path / "s1" / n) for n in os.listdir(tmp_path / "s1")) <= 1 << 20
+    assert np.array_equal(np.load(tmp_path / "s1" / "1.running_var.npy"), np.load(tmp_path / "whole" / "1.running_var.npy"))
