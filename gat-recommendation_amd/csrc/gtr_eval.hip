@@ -262,3 +262,174 @@ extern "C" int gtr_score_topk_masked(const float* se, int B, int dim, const floa
   }
   return GTR_OK;
 }
+
+// ---- target rank: Recall@K / NDCG@K without a selection ---------------------------------
+// The metrics read one number per session: how many catalog rows k_topk_chunk's order puts
+// ahead of the target.  k_rank_target computes each target's own key with the scan's MFMA
+// chain (B operand = the gathered target rows, result on the tile's diagonal: bitwise the
+// score k_rank_scan computes for that row) and seeds the output slot; k_rank_scan walks the
+// table like k_topk_chunk but compares each 16-row tile as it leaves the MFMA (no sc[NT],
+// no argmax, no candidates) and counts with ballot + popcount.  Chunk counts are combined
+// by integer atomic adds: order-independent, so deterministic.
+namespace {
+
+using namespace gtr;
+
+// Output index of session b: b + (*pos - *base) (pos == nullptr: b); -1 = not written.
+__device__ __forceinline__ int64_t rank_slot(int b, const int64_t* pos, const int64_t* base, int64_t cap) {
+  const int64_t q = (pos ? *pos - *base : (int64_t)0) + b;
+  return q >= 0 && q < cap ? q : (int64_t)-1;
+}
+
+// One wave per 16 sessions.  tkey[b] = key(b, target[b]) (all ones for a target outside
+// [0, T): nothing outranks it, and its slot is seeded with T); rank slot = 0 otherwise.
+template <int D>
+__global__ __launch_bounds__(64) void k_rank_target(const float* __restrict__ se, int B,
+                                                    const float* __restrict__ table, int T,
+                                                    const int32_t* __restrict__ target,
+                                                    uint64_t* __restrict__ tkey, int32_t* __restrict__ rank,
+                                                    int64_t rank_cap, const int64_t* __restrict__ pos,
+                                                    const int64_t* __restrict__ base) {
+  constexpr int KC = D / 16;
+  const int lane = threadIdx.x & 63;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int s0 = blockIdx.x * 16;
+  const int s = s0 + lr;
+  const bool sok = s < B;
+  const int t = sok ? target[s] : -1;
+  const bool tok = t >= 0 && t < T;
+  const float* pa = se + (size_t)(sok ? s : 0) * D + lg * 4;
+  const float* pb = table + (size_t)(tok ? t : 0) * D + lg * 4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kc = 0; kc < KC; ++kc) {
+    const float4 a = sok ? *reinterpret_cast<const float4*>(pa + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 b = tok ? *reinterpret_cast<const float4*>(pb + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+    acc = mfma4(a, b, acc);
+  }
+  // acc[i] = score(session s0 + lg*4 + i, target of session s0 + lr): the diagonal lr == lg*4 + i
+  if (sok && (lr >> 2) == lg) {
+    const int i = lr & 3;
+    const float sc = i == 0 ? acc[0] : (i == 1 ? acc[1] : (i == 2 ? acc[2] : acc[3]));
+    tkey[s] = tok ? make_key(sc, t) : ~0ull;
+    const int64_t q = rank_slot(s, pos, base, rank_cap);
+    if (q >= 0) rank[q] = tok ? 0 : T;
+  }
+}
+
+// blockIdx.x = chunk (rows [c*ch, +ch), ch a multiple of 16), blockIdx.y = session group.
+template <int D, int NSW>
+__global__ __launch_bounds__(64 * NSW) void k_rank_scan(const float* __restrict__ se, int B,
+                                                        const float* __restrict__ table, int T, int ch,
+                                                        const uint64_t* __restrict__ tkey,
+                                                        int32_t* __restrict__ rank, int64_t rank_cap,
+                                                        const int64_t* __restrict__ pos,
+                                                        const int64_t* __restrict__ base) {
+  constexpr int KC = D / 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int s0 = (blockIdx.y * NSW + wave) * 16;
+  if (s0 >= B) return;  // whole wave idle (no barriers below)
+  const int r0 = blockIdx.x * ch;
+  const int r1 = min(r0 + ch, T);
+  float4 af[KC];
+  {
+    const bool ok = s0 + lr < B;
+    const float* p = se + (size_t)(ok ? s0 + lr : 0) * D + lg * 4;
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc)
+      af[kc] = ok ? *reinterpret_cast<const float4*>(p + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  uint64_t tk[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int s = s0 + lg * 4 + i;
+    tk[i] = s < B ? tkey[s] : ~0ull;
+  }
+  int cnt[4] = {0, 0, 0, 0};
+  for (int rt = r0; rt < r1; rt += 16) {  // wave-uniform trip count
+    const int row = rt + lr;
+    const bool ok = row < T;
+    const float* p = table + (size_t)(ok ? row : 0) * D + lg * 4;
+    float4 bf[KC];
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc)
+      bf[kc] = ok ? *reinterpret_cast<const float4*>(p + kc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) acc = mfma4(af[kc], bf[kc], acc);
+    // acc[i] = score(session s0 + lg*4 + i, row): that session's 16 rows sit in lane group lg
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool ahead = ok && make_key(acc[i], row) > tk[i];
+      const uint64_t m = __ballot(ahead);
+      cnt[i] += __popc((uint32_t)(m >> (lg * 16)) & 0xFFFFu);
+    }
+  }
+  if (lr == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = s0 + lg * 4 + i;
+      if (s < B && cnt[i] > 0) {
+        const int64_t q = rank_slot(s, pos, base, rank_cap);
+        if (q >= 0) atomicAdd(rank + q, cnt[i]);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int gtr_target_rank_workspace_bytes(int B, int num_items, size_t* bytes) {
+  if (!bytes || B <= 0 || num_items <= 0) {
+    set_error("gtr_target_rank_workspace_bytes: bad arguments (B=%d T=%d)", B, num_items);
+    return GTR_E_ARG;
+  }
+  *bytes = (size_t)B * sizeof(uint64_t);  // the targets' keys
+  return GTR_OK;
+}
+
+extern "C" int gtr_target_rank(const float* se, int B, int dim, const float* table, int num_items,
+                               const int32_t* target, int32_t* rank, int64_t rank_cap, const int64_t* pos,
+                               const int64_t* base, void* ws, size_t ws_bytes, gtr_stream_t stream) {
+  size_t need = 0;
+  if (int e = gtr_target_rank_workspace_bytes(B, num_items, &need)) return e;
+  if (!se || !table || !target || !rank || rank_cap < 0 || (pos != nullptr) != (base != nullptr) || !ws ||
+      ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 7)) {
+    set_error("gtr_target_rank: bad arguments (workspace %zu < %zu bytes? pos and base go together)", ws_bytes,
+              need);
+    return GTR_E_ARG;
+  }
+  if (!(dim == 32 || dim == 64 || dim == 128 || dim == 256)) {
+    set_error("gtr_target_rank: dim %d unsupported (32/64/128/256)", dim);
+    return GTR_E_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  uint64_t* tkey = reinterpret_cast<uint64_t*>(ws);
+  const int nsw = B > 32 ? 4 : (B > 16 ? 2 : 1);
+  const int ngrp = (B + 16 * nsw - 1) / (16 * nsw);
+  // rows per workgroup: as long as the grid still fills the chip a few times over (no sc[NT]
+  // to hold, so a workgroup can walk any number of tiles with its sessions kept in registers)
+  int ch = 2048;
+  while (ch > 256 && (int64_t)((num_items + ch - 1) / ch) * ngrp < 1024) ch >>= 1;
+  const dim3 g0((B + 15) / 16), g1((num_items + ch - 1) / ch, ngrp);
+#define RK_LAUNCH(DD, NS) hipLaunchKernelGGL((k_rank_scan<DD, NS>), g1, dim3(64 * NS), 0, s, se, B, table, num_items, \
+                                             ch, tkey, rank, rank_cap, pos, base)
+#define RK_DIM(DD)                                                                                                  \
+  hipLaunchKernelGGL((k_rank_target<DD>), g0, dim3(64), 0, s, se, B, table, num_items, target, tkey, rank, rank_cap, \
+                     pos, base);                                                                                    \
+  GTR_HIP_CHECK_LAUNCH();                                                                                           \
+  if (nsw == 4) RK_LAUNCH(DD, 4);                                                                                   \
+  else if (nsw == 2) RK_LAUNCH(DD, 2);                                                                              \
+  else RK_LAUNCH(DD, 1);
+  switch (dim) {
+    case 32: RK_DIM(32) break;
+    case 64: RK_DIM(64) break;
+    case 128: RK_DIM(128) break;
+    default: RK_DIM(256) break;
+  }
+#undef RK_DIM
+#undef RK_LAUNCH
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}

@@ -198,6 +198,8 @@ _SIGS = {
     "gtr_topk_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "gtr_score_topk": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, C.c_size_t, P]),
     "gtr_score_topk_masked": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P, C.c_size_t, P]),
+    "gtr_target_rank_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "gtr_target_rank": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, i64, P, P, P, C.c_size_t, P]),
 }
 
 EXPORTS = tuple(_SIGS)

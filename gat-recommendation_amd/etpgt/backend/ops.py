@@ -320,3 +320,62 @@ def score_topk(se: torch.Tensor, table: torch.Tensor, k: int, exclude: list | No
     ptr_d = torch.tensor(ptr, dtype=torch.int32, device=se.device)
     ids_d = torch.tensor(ids, dtype=torch.int32, device=se.device)
     return torch.ops.etpgt.score_topk(se, table, int(k), ptr_d, ids_d)
+
+
+_RANK_WS: dict = {}
+
+
+def _rank_ws(B: int, T: int, dev) -> torch.Tensor:
+    """The targets' key buffer of gtr_target_rank, cached per (device, size) like _TOPK_WS."""
+    nb = C.c_size_t(0)
+    L.check(L.lib().gtr_target_rank_workspace_bytes(B, T, C.byref(nb)), "target_rank_workspace_bytes")
+    key = (str(dev), int(nb.value))
+    ws = _RANK_WS.get(key)
+    if ws is None:
+        _RANK_WS.clear()
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+        _RANK_WS[key] = ws
+    return ws
+
+
+@torch.library.custom_op("etpgt::target_rank", mutates_args=())
+def _target_rank_op(se: torch.Tensor, table: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Rank of each session's target in the full-catalog order of etpgt::score_topk
+    (gtr_target_rank): int32 [B]; a target outside the table ranks ``num_items``."""
+    B, D = se.shape
+    T = table.shape[0]
+    dev = se.device
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return rank
+    ws = _rank_ws(B, T, dev)
+    s = se.detach().float().contiguous()
+    t = table.detach().float().contiguous()
+    tgt = _dev_i32(target.reshape(-1), dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().gtr_target_rank(s.data_ptr(), B, D, t.data_ptr(), T, tgt.data_ptr(), rank.data_ptr(), B,
+                                    None, None, ws.data_ptr(), ws.numel(), st), "target_rank")
+    return rank
+
+
+@_target_rank_op.register_fake
+def _(se, table, target):
+    return se.new_empty(se.shape[0], dtype=torch.int32)
+
+
+def target_rank(se: torch.Tensor, table: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Position of each session's target item in the full ordering ``score_topk`` would
+    produce (score descending, lower item id first on ties), without selecting anything:
+    int32 [B] on the device.  ``rank < k`` iff the target is among the top k, and then
+    ``score_topk(se, table, k)[0][b, rank] == target[b]``; Recall@K / NDCG@K need nothing
+    else (etpgt.utils.metrics.compute_metrics_from_ranks).  A target id outside the table
+    ranks ``num_items`` (a miss at every k)."""
+    if isinstance(table, torch.nn.Embedding):
+        table = table.weight
+    if se.device.type != "cuda":
+        raise RuntimeError("predict runs on the MI355X HIP path only (tensors are on CPU)")
+    if se.dim() != 2 or table.dim() != 2 or se.shape[1] != table.shape[1]:
+        raise ValueError(f"session embeddings {tuple(se.shape)} do not match the item table {tuple(table.shape)}")
+    if target.numel() != se.shape[0]:
+        raise ValueError(f"{target.numel()} target items for {se.shape[0]} sessions")
+    return torch.ops.etpgt.target_rank(se, table, target)

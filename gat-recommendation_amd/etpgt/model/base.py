@@ -13,7 +13,7 @@ from abc import ABC, abstractmethod
 import torch
 import torch.nn as nn
 
-from etpgt.backend.ops import score_loss, score_topk
+from etpgt.backend.ops import score_loss, score_topk, target_rank
 
 
 class BaseRecommendationModel(nn.Module, ABC):
@@ -52,6 +52,13 @@ class BaseRecommendationModel(nn.Module, ABC):
         masking of seen items or row 0, as in the reference), fused scoring + top-k
         on the HIP kernel (gtr_score_topk, MFMA scores, no [B, T] matrix)."""
         return score_topk(session_embeddings, self.get_item_embeddings(), k)[0]
+
+    def rank_targets(self, session_embeddings: torch.Tensor, target_items: torch.Tensor) -> torch.Tensor:
+        """Position of every session's target in ``predict``'s full ordering (int32 [B], on
+        the device): ``rank < k`` iff ``predict(se, k)`` holds the target, at column
+        ``rank``.  One scan of the table, no selection (gtr_target_rank); what
+        Trainer.evaluate's Recall@K / NDCG@K need."""
+        return target_rank(session_embeddings, self.get_item_embeddings(), target_items)
 
     def compute_loss(self, session_embeddings: torch.Tensor, target_items: torch.Tensor,
                      negative_items: torch.Tensor) -> torch.Tensor:

@@ -21,7 +21,7 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
-from etpgt.utils.metrics import compute_ndcg_at_k, compute_recall_at_k
+from etpgt.utils.metrics import compute_metrics_from_ranks
 
 logger = logging.getLogger(__name__)
 
@@ -88,6 +88,7 @@ class Trainer:
         # device-built epochs: full batches per multi-step hipGraph (1: one graph per batch)
         self.steps_per_graph = max(1, int(os.environ.get("GTR_TRAINER_STEPS_PER_GRAPH", "32")))
         self._chunk_graph = None
+        self._evaluator = None  # DeviceEvaluator of a device-built validation set
 
     # ------------------------------------------------------------------ fused path
     def _fused_step(self):
@@ -132,6 +133,8 @@ class Trainer:
         group): call before ``dist.destroy_process_group()``, whose communicator teardown
         waits for every graph that captured one of its collectives to be destroyed."""
         self._chunk_graph = None
+        if self._evaluator is not None:
+            self._evaluator.close()
         if self._fused is not None:
             self._fused.close()
 
@@ -231,21 +234,43 @@ class Trainer:
 
     @torch.no_grad()
     def evaluate(self) -> dict:
+        """Recall@K / NDCG@K over the validation set (trainer.py:138-173), from each
+        session's target rank (``model.rank_targets``: the column ``predict`` would put the
+        target in) instead of a top-k selection per batch: the ranks stay on the device and
+        come to the host once.  A ``DeviceSessionLoader`` (one rank, ``shuffle=False``) runs
+        as a captured build -> forward -> rank chain (etpgt.train.evaluator); any other
+        iterable of batches is walked batch by batch.  Same metrics either way."""
         self._sync_table()
         self.model.eval()
-        preds, targets = [], []
+        num_items = int(self.model.item_embedding.weight.shape[0])
+        if max(self.k_values) > num_items:
+            raise RuntimeError(f"selected index k out of range (k={max(self.k_values)} > {num_items} items)")
+        ev = self._device_evaluator()
+        if ev is not None:
+            return compute_metrics_from_ranks(ev.run(), self.k_values)
+        ranks = []
         for batch in self.val_loader:
             batch = batch.to(self.device)
             se = self.model(batch)
-            preds.append(self.model.predict(se, k=max(self.k_values)).cpu())
-            targets.append(batch.target_item.cpu())
-        preds = torch.cat(preds, dim=0)
-        targets = torch.cat(targets, dim=0)
-        metrics = {}
-        for k in self.k_values:
-            metrics[f"recall@{k}"] = compute_recall_at_k(preds[:, :k], targets, k=k)
-            metrics[f"ndcg@{k}"] = compute_ndcg_at_k(preds[:, :k], targets, k=k)
-        return metrics
+            ranks.append(self.model.rank_targets(se, batch.target_item))
+        return compute_metrics_from_ranks(torch.cat(ranks, dim=0).cpu(), self.k_values)
+
+    def _device_evaluator(self):
+        """The captured validation chain when ``val_loader`` builds its batches on the
+        device and the model is a GraphTransformer; None: walk the loader."""
+        from etpgt.model.graph_transformer import GraphTransformer
+        from etpgt.train.dataloader import DeviceSessionLoader
+
+        vl = self.val_loader
+        if not (isinstance(vl, DeviceSessionLoader) and isinstance(self.model, GraphTransformer)
+                and vl.world == 1 and not vl.shuffle):
+            return None
+        ev = self._evaluator
+        if ev is None or ev.loader is not vl or ev.model is not self.model:
+            from etpgt.train.evaluator import DeviceEvaluator
+
+            self._evaluator = ev = DeviceEvaluator(self.model, vl)
+        return ev
 
     def save_checkpoint(self, is_best: bool = False) -> None:
         self._sync_optimizer_state()

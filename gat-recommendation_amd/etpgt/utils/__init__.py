@@ -2,7 +2,12 @@
 
 from etpgt.utils.io import load_config, load_json, save_json
 from etpgt.utils.logging import get_logger
-from etpgt.utils.metrics import compute_ndcg_at_k, compute_recall_at_k, compute_stratified_metrics
+from etpgt.utils.metrics import (
+    compute_metrics_from_ranks,
+    compute_ndcg_at_k,
+    compute_recall_at_k,
+    compute_stratified_metrics,
+)
 from etpgt.utils.seed import set_seed
 
 __all__ = [
@@ -12,6 +17,7 @@ __all__ = [
     "compute_recall_at_k",
     "compute_ndcg_at_k",
     "compute_stratified_metrics",
+    "compute_metrics_from_ranks",
     "set_seed",
     "get_logger",
 ]

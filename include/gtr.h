@@ -35,6 +35,8 @@
  *   gtr_readout_grid  partial count of gtr_readout_loss (host sizing).
  *   gtr_score_topk    base.py:59-78 predict (full-catalog scores + top-k), the
  *                     Recall@K / NDCG@K evaluation of trainer.py:138-173.
+ *   gtr_target_rank   the same evaluation from the target's rank alone: one scan of
+ *                     the table per batch, no selection.
  *   gtr_build_batch   dataloader.py:64-202 SessionDataset.__getitem__ + collate_fn on
  *                     the device (+ gtr_edge_hash_build, gtr_session_counts).
  *
@@ -627,6 +629,24 @@ int gtr_score_topk(const float* se, int B, int dim, const float* table, int num_
 int gtr_score_topk_masked(const float* se, int B, int dim, const float* table, int num_items, int k,
                           const int32_t* excl_ptr, const int32_t* excl_ids, int64_t* out_idx, float* out_score,
                           void* ws, size_t ws_bytes, gtr_stream_t stream);
+
+/* ---- evaluation: the target's rank (Recall@K / NDCG@K without a selection) ----------
+ * The metrics of trainer.py:138-173 read one number per session: the position of the
+ * target in gtr_score_topk's full ordering.  With key(b, j) the 64-bit key of score
+ * se[b] . table[j] and row j (order-preserving score bits, then ~row),
+ *   rank_b = #{ j in [0, T) : key(b, j) > key(b, target[b]) }
+ * (score descending, item id ascending on ties; the target's own score is computed by the
+ * scan's MFMA chain, so it never outranks itself).  A target outside [0, T) gets rank T.
+ * rank_b is stored at rank[off + b], off = *pos - *base (pos, base: device words, both or
+ * neither; NULL: off = 0); indices outside [0, rank_cap) are not written.  With pos the
+ * batch builder's ``start`` word and base the epoch's first cursor position, one captured
+ * launch serves every batch of every epoch.  dim 32 / 64 / 128 / 256.  Workspace (device,
+ * 8-byte aligned) of gtr_target_rank_workspace_bytes(B, T) bytes.                      */
+int gtr_target_rank_workspace_bytes(int B, int num_items, size_t* bytes);
+int gtr_target_rank(const float* se, int B, int dim, const float* table, int num_items,
+                    const int32_t* target, int32_t* rank, int64_t rank_cap,
+                    const int64_t* pos, const int64_t* base,
+                    void* ws, size_t ws_bytes, gtr_stream_t stream);
 
 /* ---- GPU batch constructor (etpgt.data.gpu_batch) ----------------------------------
  * SessionDataset.__getitem__ + collate_fn (dataloader.py:64-202) on the device, writing

@@ -16,6 +16,14 @@ Differences, each deliberate:
 * ``--device-batches`` (added): batches built on the GPU inside the captured training
   step (``create_dataloader(device_builder=True)``), default on for CUDA runs of the
   graph-transformer models; ``off`` keeps the host DataLoader + collate_fn.
+* ``--device-eval on`` (added, recommended): the validation set is built on the GPU too
+  (``create_dataloader(shuffle=False, device_builder=True)``) and ``Trainer.evaluate`` runs
+  each batch as one captured build -> eval forward -> target-rank chain
+  (etpgt.train.evaluator), with one device-to-host copy per epoch; the metrics are the
+  same.  The default is ``off``: with ``--num-workers 0`` the host validation loader's
+  per-sample ``torch.randint`` negatives (which nobody reads) consume the global
+  generator, so removing them changes the training order of every later epoch, and the
+  drop-in tests pin those runs.  Use ``on`` for anything else.
 * GAT / GraphSAGE are outside the hot-path scope: ``--model gat|graphsage`` raises.
 * Data parallel (added; the reference trains on one GPU): under ``torchrun`` /
   ``torch.distributed.run`` (WORLD_SIZE > 1) every process joins the default process
@@ -93,6 +101,12 @@ def parse_args(argv=None):
     p.add_argument("--shard-table", type=str, default="auto", choices=["auto", "on", "off"],
                    help="data parallel: row-shard the item table and its AdamW moments across the ranks "
                         "(auto: GTR_SHARD_TABLE=1)")
+    p.add_argument("--device-eval", type=str, default="off", choices=["on", "off"],
+                   help="on (recommended): validation runs on the GPU as one captured build -> forward -> "
+                        "target-rank chain per batch, one device-to-host copy per epoch; same metrics.  off "
+                        "(default) keeps the host validation loader: with --num-workers 0 its per-sample "
+                        "torch.randint negatives consume the global generator, and removing them would change "
+                        "the training order of every later epoch, which the pinned drop-in runs depend on")
     return p.parse_args(argv)
 
 
@@ -143,7 +157,12 @@ def main(argv=None):
     if dev_batches:
         kw.update(device_builder=True, device=args.device, seed=args.seed)
     train_loader = create_dataloader(sessions_path=args.train_sessions, shuffle=True, rank=rank, world=world, **kw)
-    val_loader = create_dataloader(sessions_path=args.val_sessions, shuffle=False, **kw)  # full set on every rank
+    if args.device_eval == "on":
+        if not (gt and on_gpu):
+            raise NotImplementedError("--device-eval on runs the graph-transformer models on the GPU")
+        kw.update(device_builder=True, device=args.device, seed=args.seed)
+    # full set on every rank (rank=0, world=1: nothing collective in evaluation)
+    val_loader = create_dataloader(sessions_path=args.val_sessions, shuffle=False, rank=0, world=1, **kw)
     if world > 1:
         logger.info(f"Data parallel: rank {rank} of {world}, global batch {world * args.batch_size} sessions")
     data_items = max(train_loader.dataset.num_items, val_loader.dataset.num_items)
