@@ -33,12 +33,10 @@ struct NoWait {
 };
 
 // Small parameters: element e of the flat buffer; its segment's gradient partials summed.
-// hdr: the batch header (segments with live_groups sum only its hdr[4] row groups' partials;
-// null: no such segment).  wait(): called after every load is issued, before `st` is first read.
+// wait(): called after every load is issued, before `st` is first read.
 template <class Wait = NoWait>
-__device__ __forceinline__ void small_body(int64_t e, const gtr_segment* segs, int nseg, const int32_t* hdr,
-                                           float* param, float* m, float* v, float* grad_out, const AdamStep& st,
-                                           Wait wait = Wait{}) {
+__device__ __forceinline__ void small_body(int64_t e, const gtr_segment* segs, int nseg, float* param, float* m,
+                                           float* v, float* grad_out, const AdamStep& st, Wait wait = Wait{}) {
   int s = -1;
   for (int i = 0; i < nseg; ++i)
     if (e >= segs[i].begin && e < segs[i].begin + segs[i].len) s = i;
@@ -47,16 +45,13 @@ __device__ __forceinline__ void small_body(int64_t e, const gtr_segment* segs, i
   const int64_t off = e - sg.begin;
   float g = 0.0f;
   const int np = sg.nparts;
-  // live row groups (wfold partials): the count is loaded beside the partials, not before
-  // them (every partial slot is allocated; dead groups' slots are read and skipped)
-  const int live = (sg.live_groups && hdr) ? hdr[4] : np;
   for (int p0 = 0; p0 < np; p0 += 8) {
     float pv[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) pv[u] = p0 + u < np ? sg.src[(int64_t)(p0 + u) * sg.pstride + off] : 0.0f;
 #pragma unroll
     for (int u = 0; u < 8; ++u)
-      if (p0 + u < live) g += pv[u];
+      if (p0 + u < np) g += pv[u];
   }
   if (grad_out) {
     grad_out[e] = g;

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(GTR_BLOCK) void k_shard_pack(PackK a) {
   }
   const int sb = blockIdx.x - a.nb_rows;
   const AdamStep unused{};
-  small_body((int64_t)sb * GTR_BLOCK + tid, a.segs, a.nseg, a.bt.hdr, nullptr, nullptr, nullptr, a.small_pack,
+  small_body((int64_t)sb * GTR_BLOCK + tid, a.segs, a.nseg, nullptr, nullptr, nullptr, a.small_pack,
              unused);
   if (a.small_stride > 0) {  // the small pack rides in every peer's gradient block
     __syncthreads();

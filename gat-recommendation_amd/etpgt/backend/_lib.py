@@ -38,7 +38,6 @@ class GtrConfig(C.Structure):
         ("row_group", i32), ("training", i32), ("dropout", f32), ("bn_eps", f32),
         ("bn_momentum", f32), ("seed", u32), ("rng_ctr", P), ("consumer_reduce", i32), ("sync_bn", i32),
         ("sweep", P), ("begin", P), ("ctr_add", i32), ("split_sync", i32), ("loss_batch", f32),
-        ("wfold_stride", i64),
     ]
 
 
@@ -53,7 +52,7 @@ class GtrLayer(C.Structure):
         ("xin", P), ("qkvs", P), ("alpha", P), ("agg", P), ("gate", P), ("out", P),
         ("bn_stats", P), ("bn_part", P), ("bn_gsum", P), ("bn_gpart", P), ("cnt", P),
         ("dy", P), ("dqkvs", P), ("du", P), ("dlogit", P), ("dagg", P),
-        ("bn_part_all", P), ("bn_gpart_all", P), ("nparts_fwd", i32), ("nparts_bwd", i32), ("wfold", P),
+        ("bn_part_all", P), ("bn_gpart_all", P), ("nparts_fwd", i32), ("nparts_bwd", i32),
         ("ffn", P),
     ]
 
@@ -79,7 +78,7 @@ class GtrHead(C.Structure):
 
 class GtrSegment(C.Structure):
     _fields_ = [
-        ("begin", i64), ("len", i64), ("src", P), ("pstride", i64), ("nparts", i32), ("live_groups", i32),
+        ("begin", i64), ("len", i64), ("src", P), ("pstride", i64), ("nparts", i32), ("pad", i32),
     ]
 
 
@@ -101,7 +100,7 @@ class GtrTail(C.Structure):
 
 
 SWEEP_SLOTS = 8
-ABI_VERSION = 8  # GTR_ABI_VERSION of include/gtr.h
+ABI_VERSION = 9  # GTR_ABI_VERSION of include/gtr.h
 
 
 class GtrLazy(C.Structure):

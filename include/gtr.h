@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GTR_ABI_VERSION 8 /* 8: gtr_shard.cap_s / grad_stride / small_stride / pack_parts / node_mark (two-class exchange); 7: gtr_tail.loss_acc; 6: gtr_layer.ffn + gtr_ffn_fwd / gtr_ffn_bwd / gtr_ffn_wgrad (the FFN variant); 5: gtr_config.loss_batch / wfold_stride, gtr_layer.wfold, gtr_segment.live_groups, hdr[6] halo source rows; 4: gtr_step_tail_wgrad on split-K slabs; 3: gtr_config.begin / ctr_add, gtr_tail.rng_inc */
+#define GTR_ABI_VERSION 9 /* 9: the folded-weight-gradient fields of gtr_config / gtr_layer / gtr_segment (added in 5) removed; 8: gtr_shard.cap_s / grad_stride / small_stride / pack_parts / node_mark (two-class exchange); 7: gtr_tail.loss_acc; 6: gtr_layer.ffn + gtr_ffn_fwd / gtr_ffn_bwd / gtr_ffn_wgrad (the FFN variant); 5: gtr_config.loss_batch, hdr[6] halo source rows (+ three fields removed in 9); 4: gtr_step_tail_wgrad on split-K slabs; 3: gtr_config.begin / ctr_add, gtr_tail.rng_inc */
 
 #define GTR_OK 0
 #define GTR_E_ARG 1001      /* bad argument / unsupported shape */
@@ -145,8 +145,6 @@ typedef struct gtr_config {
                               the batch's own B (a halo cut gives ranks unequal session
                               counts: loss_batch = global B / P makes the rank average of
                               the gradients the global batch's mean)                      */
-  int64_t wfold_stride;    /* > 0: weight gradients folded into gtr_conv_bwd (gtr_layer.wfold;
-                              the segments read them with live_groups = 1); 0: gtr_wgrad    */
 } gtr_config;
 
 
@@ -189,9 +187,6 @@ typedef struct gtr_layer {
   const float* bn_gpart_all; /* sync_bn: every rank's backward partials [nparts_bwd][2D]   */
   int32_t nparts_fwd;
   int32_t nparts_bwd;
-  float* wfold;              /* gtr_config.wfold_stride > 0: gtr_conv_bwd writes each row group's
-                                split-K partial of this layer's weight gradients (w_all | b_all |
-                                w_beta at the gtr_wgrad slab offsets) at wfold + g * stride     */
   const struct gtr_ffn* ffn; /* NULL, or this layer's feed-forward block (use_ffn=True; split
                                 layer path only): the next layer's gtr_qkvs_fwd then takes its
                                 input rows from ffn->z as they are, and its gtr_qkvs_bwd writes
@@ -335,8 +330,7 @@ typedef struct gtr_segment {
   const float* src;   /* gradient partials                                  */
   int64_t pstride;    /* distance between partials                           */
   int32_t nparts;
-  int32_t live_groups; /* 1: sum only the batch's live row groups (min(nparts, hdr[4])):
-                          partials written per row group by gtr_conv_bwd (wfold)     */
+  int32_t pad;
 } gtr_segment;
 
 typedef struct gtr_adam {

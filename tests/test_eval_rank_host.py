@@ -87,7 +87,7 @@ def test_abi_declares_exports_and_binds_target_rank():
         assert name in fns, f"{name} not declared in include/gtr.h"
         assert hasattr(h, name), f"{name} not exported by libgtr_hip.so"
         assert name in _lib.EXPORTS
-    assert _lib.lib().gtr_abi_version() == 8
+    assert _lib.lib().gtr_abi_version() == 9
 
 
 def test_target_rank_null_arguments_return_an_error():
