@@ -527,7 +527,8 @@ struct TailK {
   gtr_tail tl;
   gtr_adam opt;
   int T, nb_rows, nb_small, nb_sweep;
-  int windowed, pad_w;  // 1: rows part = one block per TW-slot window of the sorted list
+  int windowed;         // 1: rows part = one block per TW-slot window of the sorted list
+  int seg_wave;         // 1: every wave of the small part lies in one segment (small_body_wave)
   int64_t vbegin;       // first float4 of the untouched-row sweep (rows below: swept in the chain)
   int64_t nvec;
   int vpr_log2, nseg;
@@ -611,6 +612,9 @@ __global__ __launch_bounds__(DEFER ? GTR_TAIL_BLOCK : GTR_BLOCK) __attribute__((
         s_st.init(a.opt, t);
         s_t = (int32_t)t;
         __hip_atomic_store(&s_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        // fused begin: the step's dropout counter (here, not in a body wave: its load would
+        // hold up that wave's own)
+        if (blockIdx.x == 0 && a.tl.rng_inc) *a.tl.rng_inc += 1;
       }
       return;
     }
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(DEFER ? GTR_TAIL_BLOCK : GTR_BLOCK) __attribute__((
       __builtin_amdgcn_s_sleep(1);
   };
   const int blk = blockIdx.x;
-  if (blk == 0 && tid == 0 && a.tl.rng_inc) *a.tl.rng_inc += 1;  // fused begin: the step's dropout counter
+  if (!DEFER && blk == 0 && tid == 0 && a.tl.rng_inc) *a.tl.rng_inc += 1;
   if (blk < a.nb_rows && a.windowed) {
     wait();
     const AdamStep st = s_st;
@@ -643,17 +647,29 @@ __global__ __launch_bounds__(DEFER ? GTR_TAIL_BLOCK : GTR_BLOCK) __attribute__((
   }
   if (blk < a.nb_rows + a.nb_small) {
     const int sb = blk - a.nb_rows;
-    small_body((int64_t)sb * GTR_BLOCK + tid, a.segs, a.nseg, a.tl.flat, a.tl.flat_m, a.tl.flat_v, nullptr,
-               s_st, wait);
-    if (sb == 0 && a.tl.loss_part) {  // loss of the step: the readout's partials, fixed order
+    // loss of the step (block 0): the readout's partials, fixed order.  The first round of
+    // partials is requested before the parameters' loads, not after their stores.
+    const bool loss = sb == 0 && a.tl.loss_part;
+    const int lnp = loss ? a.tl.loss_nparts : 0;
+    float2 lp = make_float2(0.f, 0.f);
+    if (tid < lnp) lp = make_float2(a.tl.loss_part[(size_t)tid * 2], a.tl.loss_part[(size_t)tid * 2 + 1]);
+    if (a.seg_wave)
+      small_body_wave((int64_t)sb * GTR_BLOCK + tid, a.segs, a.nseg, a.tl.flat, a.tl.flat_m, a.tl.flat_v, s_st, wait);
+    else
+      small_body((int64_t)sb * GTR_BLOCK + tid, a.segs, a.nseg, a.tl.flat, a.tl.flat_m, a.tl.flat_v, nullptr,
+                 s_st, wait);
+    if (loss) {
       float acc = 0.0f;
-      for (int q = tid; q < a.tl.loss_nparts; q += GTR_BLOCK)
+      if (tid < lnp) acc += lp.x + lp.y;
+      for (int q = tid + GTR_BLOCK; q < lnp; q += GTR_BLOCK)
         acc += a.tl.loss_part[(size_t)q * 2] + a.tl.loss_part[(size_t)q * 2 + 1];
       s_acc[tid] = acc;
       __syncthreads();
       if (tid == 0) {
+        // (threads past the partial count hold +0: adding them changes nothing, they are skipped)
         float t = 0.0f;
-        for (int q = 0; q < GTR_BLOCK; ++q) t += s_acc[q];
+        const int nq = lnp < GTR_BLOCK ? lnp : GTR_BLOCK;
+        for (int q = 0; q < nq; ++q) t += s_acc[q];
         a.tl.loss_out[0] = t;
         if (a.tl.loss_acc) a.tl.loss_acc[0] += (double)t;
       }
@@ -800,6 +816,57 @@ __global__ __launch_bounds__(GTR_BLOCK) void k_step_tail_wgrad(TailWK a) {
       a.tl.loss_acc[0] += (double)a.tl.loss_out[0];
     }
   }
+}
+
+// ---- small batches: the touched rows beside the weight gradients ------------------------
+// Workgroups: [weight-gradient tile chunks | touched rows].  The tiles are k_wgrad's
+// (wgrad_block: same jobs, chunks and slabs); the touched rows are k_step_tail's rows part
+// (rows_body, same thread-to-element map).  The rows read the step begin's sorted keys,
+// the readout's coefficients and conv_bwd(0)'s dx0 and write only the item table, its
+// moments and the stamps -- nothing the tiles read or write -- so the two roles share a
+// launch with no communication: every workgroup is independent.  The tiles come first:
+// they are the launch's critical path and the rows finish under their cover (the only
+// wait is a row workgroup's own waves on its own scalar wave, as in k_step_tail).
+struct WgradRowsK {
+  WgradK w;
+  gtr_batch bt;
+  gtr_tail tl;
+  gtr_adam opt;
+  int T, nb_wg;
+};
+
+template <int D>
+__global__ __launch_bounds__(GTR_TAIL_BLOCK) void k_wgrad_rows(WgradRowsK a) {
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  if (blk < a.nb_wg) {
+    if (tid >= GTR_BLOCK) return;  // the rows' step-scalar wave: nothing to do for a tile
+    wgrad_block(a.w, blk);
+    return;
+  }
+  // as k_step_tail<D, true>: a fifth wave computes the step's AdamW scalars while the body
+  // waves issue their loads (with one thread and a barrier ahead of the loads the rows were
+  // the launch's last workgroups: + 0.7 us on the launch at C2 against + 0.3 this way)
+  __shared__ AdamStep s_st;
+  __shared__ int32_t s_t;
+  __shared__ int s_ready;
+  if (tid == 0) s_ready = 0;
+  __syncthreads();
+  if (tid >= GTR_BLOCK) {
+    if (tid == GTR_BLOCK) {
+      const int64_t t = *a.opt.step_dev + a.opt.step_offset;
+      s_st.init(a.opt, t);
+      s_t = (int32_t)t;
+      __hip_atomic_store(&s_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return;
+  }
+  auto wait = [&]() {
+    while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+      __builtin_amdgcn_s_sleep(1);
+  };
+  rows_body<D>((blk - a.nb_wg) * GTR_BLOCK + tid, a.bt, a.T, a.tl.skeys, a.tl.svals, a.tl.dx0, a.tl.se,
+               a.tl.coef_tgt, a.tl.coef_neg, a.tl.table, a.tl.table_m, a.tl.table_v, nullptr, s_st,
+               a.tl.lazy_consts ? a.tl.stamp : nullptr, s_t, wait);
 }
 
 template <int D>
@@ -1734,18 +1801,21 @@ int gtr_lazy_flush(int num_items, int dim, int32_t* stamp, const int64_t* step_d
   return GTR_OK;
 }
 
-int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail, const gtr_segment* segs,
-                  int nseg, const gtr_adam* opt, gtr_stream_t stream) {
+// gtr_step_tail / gtr_step_tail_small (small_only: no rows part -- the touched rows ran in
+// gtr_wgrad_rows)
+static int step_tail(const char* who, bool small_only, const gtr_batch* bt, int num_items, int dim,
+                     const gtr_tail* tail, const gtr_segment* segs, int nseg, const gtr_adam* opt,
+                     gtr_stream_t stream) {
   if (!bt || !tail || !opt || !opt->step_dev || !dim_ok(dim) || num_items <= 0 || nseg < 0 ||
       nseg > GTR_SMALL_MAX_SEG || (nseg > 0 && !segs)) {
-    set_error("gtr_step_tail: bad arguments");
+    set_error("%s: bad arguments", who);
     return GTR_E_ARG;
   }
   const gtr_tail& t = *tail;
   if (!t.skeys || !t.svals || !t.dx0 || !t.se || !t.coef_tgt || !t.coef_neg || !t.table || !t.table_m ||
       !t.table_v || !t.stamp || (nseg > 0 && (!t.flat || !t.flat_m || !t.flat_v)) ||
       (t.loss_part && (!t.loss_out || t.loss_nparts < 0))) {
-    set_error("gtr_step_tail: missing buffers");
+    set_error("%s: missing buffers", who);
     return GTR_E_ARG;
   }
   TailK k{};
@@ -1756,8 +1826,14 @@ int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* t
   const int m_cap = bt->n_cap + bt->b_cap * (1 + bt->n_neg);
   hipStream_t s = (hipStream_t)stream;
   k.windowed = m_cap > GTR_BEGIN_MCAP ? 1 : 0;
-  if (k.windowed) {
-    if (!t.carry) { set_error("gtr_step_tail: large batch (m_cap > %d) needs the carry scratch", GTR_BEGIN_MCAP); return GTR_E_ARG; }
+  if (small_only) {
+    if (k.windowed) {
+      set_error("%s: batch too large (m_cap %d > %d): use gtr_wgrad + gtr_step_tail", who, m_cap, GTR_BEGIN_MCAP);
+      return GTR_E_ARG;
+    }
+    k.nb_rows = 0;
+  } else if (k.windowed) {
+    if (!t.carry) { set_error("%s: large batch (m_cap > %d) needs the carry scratch", who, GTR_BEGIN_MCAP); return GTR_E_ARG; }
     const int nwin = (m_cap + TW - 1) / TW;
     k.nb_rows = nwin;
     if (nwin > 1) {
@@ -1786,6 +1862,8 @@ int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* t
   k.nb_sweep = (int)(sw > 2048 ? 2048 : sw);
   k.nseg = nseg;
   for (int i = 0; i < nseg; ++i) k.segs[i] = segs[i];
+  const char* sw_env = getenv("GTR_SMALL_WAVE");  // A/B: 0 = small_body's per-element segment search
+  k.seg_wave = small_segs_wave_ok(segs, nseg) && !(sw_env && sw_env[0] == '0') ? 1 : 0;
   const int grid = k.nb_rows + k.nb_small + k.nb_sweep;
   switch (dim) {
 #define GTR_TAIL(DD) if (k.windowed) hipLaunchKernelGGL((k_step_tail<DD, false>), dim3(grid), dim3(GTR_BLOCK), 0, s, k); \
@@ -1795,6 +1873,61 @@ int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* t
     case 128: GTR_TAIL(128); break;
     default: GTR_TAIL(256); break;
 #undef GTR_TAIL
+  }
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}
+
+int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail, const gtr_segment* segs,
+                  int nseg, const gtr_adam* opt, gtr_stream_t stream) {
+  return step_tail("gtr_step_tail", false, bt, num_items, dim, tail, segs, nseg, opt, stream);
+}
+
+int gtr_step_tail_small(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail, const gtr_segment* segs,
+                        int nseg, const gtr_adam* opt, gtr_stream_t stream) {
+  return step_tail("gtr_step_tail_small", true, bt, num_items, dim, tail, segs, nseg, opt, stream);
+}
+
+int gtr_wgrad_rows(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* dx0,
+                   const float* pe_tab, float* const* layer_slab, float* pe_slab, int n_chunks, int64_t slab_stride,
+                   int l_begin, int l_end, int num_items, const gtr_tail* tail, const gtr_adam* opt,
+                   gtr_stream_t stream) {
+  if (!cfg || !bt || !tail || !opt || !opt->step_dev || !dim_ok(cfg->dim) || num_items <= 0) {
+    set_error("gtr_wgrad_rows: bad arguments");
+    return GTR_E_ARG;
+  }
+  const gtr_tail& t = *tail;
+  const int D = cfg->dim;
+  const int m_cap = bt->n_cap + bt->b_cap * (1 + bt->n_neg);
+  if (m_cap > GTR_BEGIN_MCAP) {
+    set_error("gtr_wgrad_rows: batch too large (m_cap %d > %d): use gtr_wgrad + gtr_step_tail", m_cap,
+              GTR_BEGIN_MCAP);
+    return GTR_E_ARG;
+  }
+  if (!t.skeys || !t.svals || !t.dx0 || !t.se || !t.coef_tgt || !t.coef_neg || !t.table || !t.table_m ||
+      !t.table_v || !t.stamp) {
+    set_error("gtr_wgrad_rows: missing buffers");
+    return GTR_E_ARG;
+  }
+  WgradRowsK k{};
+  int wblocks = 0;
+  if (const int rc = fill_wgrad("gtr_wgrad_rows", cfg, bt, layers, dx0, pe_tab, layer_slab, pe_slab, n_chunks,
+                                slab_stride, l_begin, l_end, k.w, wblocks))
+    return rc;
+  k.bt = *bt;
+  k.tl = t;
+  k.opt = *opt;
+  k.T = num_items;
+  k.nb_wg = wblocks;
+  const int nb_rows = (int)(((int64_t)m_cap * (D / 4) + GTR_BLOCK - 1) / GTR_BLOCK);
+  const int grid = wblocks + nb_rows;
+  if (grid == 0) return GTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  switch (D) {
+    case 32: hipLaunchKernelGGL(k_wgrad_rows<32>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    case 64: hipLaunchKernelGGL(k_wgrad_rows<64>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    case 128: hipLaunchKernelGGL(k_wgrad_rows<128>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    default: hipLaunchKernelGGL(k_wgrad_rows<256>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
   }
   GTR_HIP_CHECK_LAUNCH();
   return GTR_OK;

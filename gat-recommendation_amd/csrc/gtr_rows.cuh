@@ -65,6 +65,60 @@ __device__ __forceinline__ void small_body(int64_t e, const gtr_segment* segs, i
   v[e] = vv;
 }
 
+// small_body for a whole wave of 64 consecutive elements (e - lane a multiple of 64) when
+// every segment begins at a multiple of 64 and no two overlap (small_segs_wave_ok): the
+// wave then lies in at most one segment.  small_body finds each lane's segment with two
+// dependent scalar loads per segment, reads that segment's fields through the vector path
+// (two more rounds) and only then requests the partials and, after them, p / m / v: at
+// B = 32 a chain of load latencies on the step's last launch.  Here lane i tests segment i
+// (one load round for all of them), the match is wave-uniform, so the segment's fields
+// come through the scalar path, and p / m / v are requested before the partials.  The
+// partials are summed in the same order: bitwise small_body.
+template <class Wait = NoWait>
+__device__ __forceinline__ void small_body_wave(int64_t e, const gtr_segment* segs, int nseg, float* param,
+                                                float* m, float* v, const AdamStep& st, Wait wait = Wait{}) {
+  const int lane = threadIdx.x & 63;
+  const int64_t e0 = e - lane;
+  bool hit = false;
+  if (lane < nseg) {
+    const int64_t b = segs[lane].begin, n = segs[lane].len;
+    hit = e0 >= b && e0 < b + n;
+  }
+  const unsigned long long mask = __ballot(hit);
+  if (mask == 0) return;
+  const int s = 63 - __builtin_clzll(mask);
+  const gtr_segment& sg = segs[s];
+  const int64_t off = e - sg.begin;
+  if (off >= sg.len) return;
+  float pv = param[e], mv = m[e], vv = v[e];
+  float g = 0.0f;
+  const int np = sg.nparts;
+  for (int p0 = 0; p0 < np; p0 += 8) {
+    float gp[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) gp[u] = p0 + u < np ? sg.src[(int64_t)(p0 + u) * sg.pstride + off] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (p0 + u < np) g += gp[u];
+  }
+  wait();
+  st.apply(pv, mv, vv, g);
+  param[e] = pv;
+  m[e] = mv;
+  v[e] = vv;
+}
+
+// Host: may small_body_wave stand in for small_body on these segments?
+inline bool small_segs_wave_ok(const gtr_segment* segs, int nseg) {
+  if (nseg > 64) return false;
+  for (int i = 0; i < nseg; ++i) {
+    if (segs[i].begin < 0 || segs[i].begin % 64 || segs[i].len < 0) return false;
+    for (int j = 0; j < i; ++j)
+      if (segs[i].begin < segs[j].begin + segs[j].len && segs[j].begin < segs[i].begin + segs[i].len) return false;
+  }
+  return true;
+}
+
 // Lazy table: bring one float4 column of a row from its stamp to step `upto` with the
 // zero-gradient update of each step in order (AdamStep with step t's scalars from
 // consts[t]): the same float operations as the eager sweep applies, so bitwise equal.

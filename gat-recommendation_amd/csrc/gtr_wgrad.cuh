@@ -10,6 +10,8 @@
 
 #include "gtr_common.cuh"
 
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace gtr {
@@ -41,6 +43,7 @@ struct WgradK {
   const int32_t* hdr;
   int P, njobs, D, pad0;
   int64_t stride;
+  int blk0s[GTR_MAX_WJOBS];  // jobs[i].blk0 side by side: one scalar load finds a workgroup's job
   WJob jobs[GTR_MAX_WJOBS];
 };
 
@@ -432,6 +435,84 @@ inline int build_wjobs(const gtr_config* cfg, const gtr_batch* bt, const gtr_lay
     }
     blocks += w.nt * n_chunks;
   }
+  return GTR_OK;
+}
+
+// Workgroup `blk` of a weight-gradient launch: tile local / P of its job, summed over row
+// chunk local % P into the chunk's partial slab.  Whole block (GTR_BLOCK threads).
+__device__ __forceinline__ void wgrad_block(const WgradK& a, int blk) {
+  // (the first workgroups of the jobs ascend: the job is the number of them at or below blk;
+  // walking jobs[].blk0 instead was one dependent scalar load per job)
+  int jid = 0;
+#pragma unroll
+  for (int i = 1; i < GTR_MAX_WJOBS; ++i) jid += i < a.njobs && blk >= a.blk0s[i] ? 1 : 0;
+  const WJob& J = a.jobs[jid];
+  const int local = blk - J.blk0;
+  const int tile = local / a.P, p = local - tile * a.P;
+  const int N = a.hdr[0];
+  const int per = (N + a.P - 1) / a.P;
+  const int t0 = p * per;
+  const int t1 = min(N, t0 + per);
+  const int64_t so = (int64_t)p * a.stride;
+  auto emit = [&](int which, int64_t idx, float v) {
+    if (which == 0) J.outW[so + idx] = v;
+    else J.outB[so + idx] = v;
+  };
+  auto emit4 = [&](int64_t idx, float4 v) { *reinterpret_cast<float4*>(J.outW + so + idx) = v; };
+  if (J.mfma == 1) wgrad_tile_mfma<false>(J, tile, t0, t1, emit, emit4);
+  else if (J.mfma == 2) wgrad_tile_mfma<true>(J, tile, t0, t1, emit, emit4);
+  else wgrad_tile(J, tile, t0, t1, a.D, emit);
+}
+
+// Host: the launch arguments of the split-K weight gradients of layers [l_begin, l_end)
+// (gtr_wgrad and gtr_wgrad_rows); `blocks` = tile workgroups (0: nothing to launch).
+inline int fill_wgrad(const char* who, const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers,
+                      const float* dx0, const float* pe_tab, float* const* layer_slab, float* pe_slab, int n_chunks,
+                      int64_t slab_stride, int l_begin, int l_end, WgradK& k, int& blocks) {
+  blocks = 0;
+  if (!cfg || !bt || !layers || !layer_slab || n_chunks <= 0) {
+    set_error("%s: bad arguments", who);
+    return GTR_E_ARG;
+  }
+  const int D = cfg->dim, Lc = cfg->num_layers;
+  if (3 * Lc + 1 > GTR_MAX_WJOBS) { set_error("%s: too many layers", who); return GTR_E_ARG; }
+  k.hdr = bt->hdr;
+  k.P = n_chunks;
+  k.D = D;
+  k.stride = slab_stride;
+  if (l_begin < 0 || l_end > Lc || l_begin > l_end) { set_error("%s: bad layer range", who); return GTR_E_ARG; }
+  int nj = 0;
+  // MFMA tiles for the QKVS weight once a chunk holds enough rows to amortize them
+  // (GTR_WGRAD=mfma|valu overrides; the float4 slab stores need 16 B aligned slabs)
+  const char* wm = getenv("GTR_WGRAD");
+  const int rows_per_chunk = (bt->n_cap + n_chunks - 1) / n_chunks;
+  bool mfma = rows_per_chunk >= GTR_WGRAD_MFMA_ROWS;
+  if (wm && !strcmp(wm, "mfma")) mfma = true;
+  if (wm && !strcmp(wm, "valu")) mfma = false;
+  if (slab_stride % 4) mfma = false;
+  for (int l = l_begin; l < l_end; ++l)
+    if (reinterpret_cast<uintptr_t>(layer_slab[l]) % 16) mfma = false;
+  const int rc = build_wjobs(cfg, bt, layers, dx0, pe_tab, layer_slab, pe_slab, nullptr, nullptr, n_chunks, l_begin,
+                             l_end, k.jobs, nj, blocks, mfma);
+  if (rc) return rc;
+  if (const char* jm = getenv("GTR_WGRAD_JOBS")) {  // diagnostics (timing only): keep job types in the mask
+    const int mask = atoi(jm);
+    int kept = 0;
+    blocks = 0;
+    for (int i = 0; i < nj; ++i) {
+      const bool pe = k.jobs[i].type == WJ_MM && k.jobs[i].M1 == D;
+      const int bit = pe ? 8 : 1 << k.jobs[i].type;
+      if (!(mask & bit)) continue;
+      WJob j = k.jobs[i];
+      j.blk0 = blocks;
+      blocks += j.nt * n_chunks;
+      k.jobs[kept++] = j;
+    }
+    nj = kept;
+  }
+  k.njobs = nj;
+  for (int i = 0; i < nj; ++i) k.blk0s[i] = k.jobs[i].blk0;
+  if (nj == 0) blocks = 0;
   return GTR_OK;
 }
 

@@ -517,20 +517,31 @@ class Engine:
         tab = self.model.item_embedding.weight.data_ptr() if table is None else table
         return h, tab
 
-    def _wgrad(self, ws, cfg, bs, l0, l1, st):
+    def _wgrad(self, ws, cfg, bs, l0, l1, st, rows=None):
+        """Weight-gradient slabs of layers [l0, l1); ``rows`` = (tail, adam): the same
+        launch also updates the touched table rows (gtr_wgrad_rows)."""
         pe_tab = None
         if self.K > 0 and self.model.laplacian_pe._cached_pe is not None:
             pe_tab = self.model.laplacian_pe._cached_pe.data_ptr()
+        if rows is not None:
+            tail, adam = rows
+            L.check(L.lib().gtr_wgrad_rows(C.byref(cfg), C.byref(bs), ws.structs, ws.dx0.data_ptr(), pe_tab,
+                                           ws.slab_ptrs, None if ws.pe_slab is None else ws.pe_slab.data_ptr(),
+                                           ws.P, self.flat.layout.slab_stride, l0, l1, self.T, C.byref(tail),
+                                           C.byref(adam), st), "wgrad_rows")
+            return
         L.check(L.lib().gtr_wgrad(C.byref(cfg), C.byref(bs), ws.structs, ws.dx0.data_ptr(), pe_tab, ws.slab_ptrs,
                                   None if ws.pe_slab is None else ws.pe_slab.data_ptr(), ws.P,
                                   self.flat.layout.slab_stride, l0, l1, st), "wgrad")
 
     def run_backward(self, ws: Workspace, cfg: L.GtrConfig, bs: L.GtrBatch, side: torch.cuda.Stream | None = None,
-                     wgrad: bool = True, split: bool | None = None):
+                     wgrad: bool = True, split: bool | None = None, rows=None):
         """conv_bwd(L-1..0) + weight-gradient slabs; expects layers[L-1].dy / bn_gsum.
         With ``side``, layer l >= 1 weight gradients run on that stream concurrently
         with conv_bwd(l-1..0); the caller must join ``side`` before reading slabs.
-        ``wgrad=False``: the weight gradients are left to the fused tail."""
+        ``wgrad=False``: the weight gradients are left to the fused tail.  ``rows`` =
+        (tail, adam), without ``side``: the weight-gradient launch also updates the touched
+        table rows (gtr_wgrad_rows)."""
         lib = L.lib()
         main = torch.cuda.current_stream(self.device)
         st = main.cuda_stream
@@ -548,7 +559,7 @@ class Engine:
         if side is not None:
             self._wgrad(ws, cfg, bs, 0, 1, st)
         else:
-            self._wgrad(ws, cfg, bs, 0, self.L, st)
+            self._wgrad(ws, cfg, bs, 0, self.L, st, rows)
 
     def segments(self, ws: Workspace):
         """Segment table mapping each flat parameter segment to its gradient source."""

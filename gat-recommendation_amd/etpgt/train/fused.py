@@ -344,6 +344,12 @@ class FusedTrainStep:
             self.layer_flat = (C.c_int64 * (3 * eng.L))(*[lay.seg(f"{l}.{n}").begin for l in range(eng.L)
                                                           for n in ("w_all", "b_all", "w_beta")])
             self.pe_flat = (C.c_int64 * 2)(lay.seg("pe.w").begin, lay.seg("pe.b").begin) if eng.K > 0 else None
+        # single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
+        # weight-gradient launch (gtr_wgrad_rows -- the rows do not depend on the weight
+        # gradients) and the tail keeps the small parameters (gtr_step_tail_small); bitwise
+        # the two plain launches, GTR_ROWS_EARLY=0 restores them
+        self.rows_early = (self.dp is None and self.shard is None and m_cap <= 8192 and not self.tail_wgrad
+                           and os.environ.get("GTR_ROWS_EARLY", "1") != "0")
         self.graph = None
         self.graph_pe = None
         self.graph_b = None
@@ -528,7 +534,8 @@ class FusedTrainStep:
         self._begin(bs, st)
         eng.run_forward(ws, cfg, bs, L.RO_FWD | L.RO_LOSS | L.RO_BWD, self.loss_kind, self.temperature, self.alpha,
                         split=self.split)
-        eng.run_backward(ws, cfg, bs, wgrad=not self.tail_wgrad, split=self.split)
+        eng.run_backward(ws, cfg, bs, wgrad=not self.tail_wgrad, split=self.split,
+                         rows=(self.tail, self.adam) if self.rows_early else None)
         if self.dp is not None:
             self.dp.launch_pack(bs, st)
 
@@ -549,6 +556,9 @@ class FusedTrainStep:
                                                 C.byref(self.tail), self.segs_gb, self.nseg_gb, C.byref(self.adam),
                                                 self.tile_cnt.data_ptr(), self.tile_cnt.numel(), st),
                     "step_tail_wgrad")
+        elif self.rows_early:  # the touched rows ran beside the weight gradients
+            L.check(L.lib().gtr_step_tail_small(C.byref(bs), eng.T, eng.D, C.byref(self.tail), self.segs, self.nseg,
+                                                C.byref(self.adam), st), "step_tail_small")
         else:
             L.check(L.lib().gtr_step_tail(C.byref(bs), eng.T, eng.D, C.byref(self.tail), self.segs, self.nseg,
                                           C.byref(self.adam), st), "step_tail")

@@ -506,6 +506,24 @@ int gtr_step_tail_wgrad(const gtr_config* cfg, const gtr_batch* bt, const gtr_la
                         const gtr_segment* segs, int nseg, const gtr_adam* opt, uint32_t* tile_cnt, int tile_cnt_len,
                         gtr_stream_t stream);
 
+/* Small batches (m_cap <= 8192; GTR_E_ARG above): gtr_wgrad and the touched-row AdamW of
+ * gtr_step_tail as ONE launch of independent workgroups -- first the weight-gradient
+ * tiles (arguments, slabs and results exactly gtr_wgrad's), then the touched rows
+ * (tail->skeys .. table_v, stamp, lazy_consts; opt as gtr_step_tail).  The rows need the
+ * step begin, the readout and conv_bwd(0), not the weight gradients, so they finish under
+ * the tiles' cover.  Follow it with gtr_step_tail_small: the pair is bitwise equal to
+ * gtr_wgrad + gtr_step_tail.                                                          */
+int gtr_wgrad_rows(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* dx0,
+                   const float* pe_tab, float* const* layer_slab, float* pe_slab, int n_chunks, int64_t slab_stride,
+                   int l_begin, int l_end, int num_items, const gtr_tail* tail, const gtr_adam* opt,
+                   gtr_stream_t stream);
+
+/* gtr_step_tail without its touched-rows part (after gtr_wgrad_rows): the small
+ * parameters, the loss sum, tail->rng_inc and any untouched-row sweep left to the tail.
+ * Small batches only (m_cap <= 8192; GTR_E_ARG above).                                 */
+int gtr_step_tail_small(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail,
+                        const gtr_segment* segs, int nseg, const gtr_adam* opt, gtr_stream_t stream);
+
 /* ---- data-parallel step (one process per GPU; etpgt.train.distributed) --------
  * Each rank packs its gradients into `pack` (words per rank = layout.words):
  *   [0, flat_total)          summed small-parameter gradient (flat layout)
