@@ -869,6 +869,388 @@ __global__ __launch_bounds__(GTR_TAIL_BLOCK) void k_wgrad_rows(WgradRowsK a) {
                a.tl.lazy_consts ? a.tl.stamp : nullptr, s_t, wait);
 }
 
+// ---- small batches: the end of the step in ONE launch ------------------------------------
+// gtr_wgrad_rows + gtr_step_tail_small without the slabs between them.  Workgroups:
+// [weight-gradient tiles | touched rows | BatchNorm gamma / beta + loss], all independent:
+// every output of the weight-gradient jobs is owned by ONE thread, which forms the P chunk
+// values over the chunks' row ranges with wgrad_tile's operations in wgrad_tile's order,
+// adds them in chunk order from +0 (what the tail's small part does with the P slabs) and
+// applies AdamW to the flat parameter.  No slab, no counter, no second launch.
+//   * A workgroup stages the columns it needs of ALL N rows in one round (every load in
+//     flight before the first wait) into LDS, chunk p at row slot p * pad (pad = the power
+//     of two >= max(16, rows per chunk)), the slots past a chunk's rows zero.  The loops then
+//     run whole rounds of 8 (MM) / 16 (phases) slots with no bound inside.  A zero slot
+//     adds fma(0, 0, acc): that changes acc only when it is -0, and the chunk value is next
+//     added to g >= +0 (never -0: it starts at +0), where -0 and +0 give the same sum --
+//     so the zero slots (wgrad_tile has its own, up to its 32-row round) need no care.
+//   * wgrad_tile's `acc += a * b` compiles to fused multiply-adds (v_pk_fma_f32).  Here the
+//     same expression did not: the vectorizer paired the products across rows and the sums
+//     across outputs, which leaves a multiply and an add (1 ulp off).  So the products are
+//     written as fmaf(); tests/test_gpu_step_end.py holds the two forms bit for bit.
+//   * WJ_MM: 16 OM x 16 ON outputs per workgroup, OM x ON per thread; the bias of a job
+//     that carries it rides as the ones column at M2, as in wgrad_tile.
+//   * WJ_COLSUM / WJ_GATE: GTR_SE_CW columns per workgroup; thread (column, chunk) sums the
+//     16 row phases of its chunk, each in ascending rows, then the phases in order; thread
+//     (segment, column) adds the chunk values.
+#define GTR_SE_ROWS 256  // row slots one staging round holds
+#define GTR_SE_OM 2
+#define GTR_SE_ON 1
+#define GTR_SE_CW 16
+#define GTR_SE_MAXP (GTR_BLOCK / GTR_SE_CW)
+#define GTR_SE_SEGS 16
+#define GTR_SE_YOFF ((GTR_SE_ROWS + GTR_SE_MAXP) * GTR_SE_CW)  // GATE: s columns after the agg columns
+#define GTR_SE_UOFF (2 * GTR_SE_YOFF)                          // GATE: du after both
+#define GTR_SE_LDS (GTR_SE_ROWS * 16 * (GTR_SE_OM + GTR_SE_ON))
+static_assert(GTR_SE_UOFF + GTR_SE_ROWS <= GTR_SE_LDS, "GATE staging must fit the MM staging buffer");
+static_assert(GTR_BLOCK <= GTR_SE_LDS, "the loss partials reuse the staging buffer");
+
+struct SEJob {
+  int type, M1, M2, lda, ldb, tn, hasb, pad0;  // tn: tile columns (MM); hasb: ones column at M2
+  const float* A;
+  const float* B;
+  const int32_t* bidx;
+  const float* agg;
+  const float* s;
+  int64_t fW, fB;
+};
+
+struct StepEndK {
+  gtr_batch bt;
+  gtr_tail tl;
+  gtr_adam opt;
+  int T, P, D, njobs, nb_tiles, nb_rows, nb_gb, nseg;
+  int blk0s[GTR_MAX_WJOBS];  // first workgroup of each job
+  int gb0s[GTR_SE_SEGS];     // first workgroup (within the role) of each gamma / beta segment
+  SEJob jobs[GTR_MAX_WJOBS];
+  gtr_segment segs[GTR_SE_SEGS];
+};
+
+// Row chunks as k_wgrad cuts them (per = ceil(N / P)) and their padded LDS slots.
+struct SEChunks {
+  int N, per, lg;  // chunk p: rows [p * per, min(N, (p + 1) * per)) at slots p << lg
+  __device__ __forceinline__ SEChunks(const int32_t* hdr, int n_cap, int P) {
+    N = min(max(hdr[0], 0), n_cap);
+    per = (N + P - 1) / P;
+    lg = per <= 16 ? 4 : 32 - __clz(per - 1);
+  }
+  // node row of a slot, -1: a zero slot
+  __device__ __forceinline__ int row(int slot) const {
+    const int p = slot >> lg, r = slot & ((1 << lg) - 1);
+    const int t = p * per + r;
+    return r < per && t < N ? t : -1;
+  }
+};
+
+template <int OM, int ON, class Wait>
+__device__ __forceinline__ void se_mm_tile(const SEJob& J, int tile, const int32_t* hdr, int n_cap, int P, float* S,
+                                           float* fp, float* fm, float* fv, const AdamStep& s_st, Wait wait) {
+  constexpr int TM = 16 * OM, TN = 16 * ON, LS = TM + TN;  // an LDS row: TM columns of A, TN of B
+  constexpr int A4 = TM / 4, B4 = TN / 4;
+  constexpr int NQA = GTR_SE_ROWS * A4 / GTR_BLOCK, NQB = GTR_SE_ROWS * B4 / GTR_BLOCK;
+  static_assert(GTR_SE_ROWS * LS <= GTR_SE_LDS, "MM staging");
+  const int tid = threadIdx.x;
+  const int tm = tile / J.tn, tq = tile - tm * J.tn;
+  const int m0 = tm * TM, n0 = tq * TN;
+  const int ty = tid >> 4, tx = tid & 15;
+  const SEChunks ch(hdr, n_cap, P);
+  // this thread's outputs and their p / m / v: requested ahead of the rows
+  int64_t e[OM][ON];
+  float pv[OM][ON], mv[OM][ON], vv[OM][ON];
+#pragma unroll
+  for (int i = 0; i < OM; ++i)
+#pragma unroll
+    for (int q = 0; q < ON; ++q) {
+      const int m = m0 + ty * OM + i, n = n0 + tx * ON + q;
+      e[i][q] = -1;
+      if (m < J.M1) {
+        if (n < J.M2) e[i][q] = J.fW + (int64_t)m * J.M2 + n;
+        else if (n == J.M2 && J.hasb) e[i][q] = J.fB + m;
+      }
+      pv[i][q] = mv[i][q] = vv[i][q] = 0.0f;
+      if (e[i][q] >= 0) {
+        pv[i][q] = fp[e[i][q]];
+        mv[i][q] = fm[e[i][q]];
+        vv[i][q] = fv[e[i][q]];
+      }
+    }
+  // one staging round: B's row ids first (the LapPE gather), then every row load
+  int tb[NQB];
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) {
+    const int t = ch.row((tid + q * GTR_BLOCK) / B4);
+    tb[q] = t >= 0 && J.bidx ? J.bidx[t] : t;
+  }
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 av[NQA], bv[NQB];
+#pragma unroll
+  for (int q = 0; q < NQA; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    const int t = ch.row(idx / A4), col = m0 + (idx % A4) * 4;
+    av[q] = z4;
+    if (t >= 0 && col < J.M1) av[q] = *reinterpret_cast<const float4*>(J.A + (size_t)t * J.lda + col);
+  }
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    const int col = n0 + (idx % B4) * 4;
+    bv[q] = z4;
+    if (tb[q] >= 0) {
+      if (col < J.M2) bv[q] = *reinterpret_cast<const float4*>(J.B + (size_t)tb[q] * J.ldb + col);
+      else if (col == J.M2 && J.hasb) bv[q].x = 1.0f;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQA; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    *reinterpret_cast<float4*>(S + (idx / A4) * LS + (idx % A4) * 4) = av[q];
+  }
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    *reinterpret_cast<float4*>(S + (idx / B4) * LS + TM + (idx % B4) * 4) = bv[q];
+  }
+  __syncthreads();
+  float g[OM][ON];
+#pragma unroll
+  for (int i = 0; i < OM; ++i)
+#pragma unroll
+    for (int q = 0; q < ON; ++q) g[i][q] = 0.0f;
+  for (int p = 0; p < P; ++p) {
+    const int t0 = p * ch.per;
+    if (t0 >= ch.N) break;  // an empty chunk adds +0
+    const int nr = min(ch.N - t0, ch.per);
+    const float* Sp = S + (p << ch.lg) * LS;
+    float acc[OM][ON];
+#pragma unroll
+    for (int i = 0; i < OM; ++i)
+#pragma unroll
+      for (int q = 0; q < ON; ++q) acc[i][q] = 0.0f;
+    for (int k0 = 0; k0 < nr; k0 += 8) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float* r = Sp + (k0 + k) * LS;
+        float ar[OM], br[ON];
+#pragma unroll
+        for (int i = 0; i < OM; ++i) ar[i] = r[ty * OM + i];
+#pragma unroll
+        for (int q = 0; q < ON; ++q) br[q] = r[TM + tx * ON + q];
+#pragma unroll
+        for (int i = 0; i < OM; ++i)
+#pragma unroll
+          for (int q = 0; q < ON; ++q) acc[i][q] = __builtin_fmaf(ar[i], br[q], acc[i][q]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < OM; ++i)
+#pragma unroll
+      for (int q = 0; q < ON; ++q) g[i][q] += acc[i][q];
+  }
+  wait();
+  const AdamStep st = s_st;
+#pragma unroll
+  for (int i = 0; i < OM; ++i)
+#pragma unroll
+    for (int q = 0; q < ON; ++q) {
+      if (e[i][q] < 0) continue;
+      st.apply(pv[i][q], mv[i][q], vv[i][q], g[i][q]);
+      fp[e[i][q]] = pv[i][q];
+      fm[e[i][q]] = mv[i][q];
+      fv[e[i][q]] = vv[i][q];
+    }
+}
+
+template <class Wait>
+__device__ __forceinline__ void se_col_tile(const SEJob& J, int tile, const int32_t* hdr, int n_cap, int P, int D,
+                                            float* S, float (*cv)[GTR_SE_MAXP][GTR_SE_CW], float* fp, float* fm,
+                                            float* fv, const AdamStep& s_st, Wait wait) {
+  constexpr int CW = GTR_SE_CW, C4 = CW / 4, NQ = GTR_SE_ROWS * C4 / GTR_BLOCK;
+  static_assert(GTR_SE_ROWS == GTR_BLOCK, "one du word per thread");
+  const int tid = threadIdx.x;
+  const bool gate = J.type == WJ_GATE;
+  const int c0 = tile * CW;
+  const SEChunks ch(hdr, n_cap, P);
+  // the threads that own an output: (segment, column); their p / m / v first
+  const int nown = gate ? 3 * CW : CW;
+  const int64_t e = gate ? J.fW + (int64_t)(tid / CW) * D + c0 + tid % CW : J.fB + c0 + tid % CW;
+  float pv = 0.0f, mv = 0.0f, vv = 0.0f;
+  if (tid < nown) {
+    pv = fp[e];
+    mv = fm[e];
+    vv = fv[e];
+  }
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float* X = gate ? J.agg : J.A;
+  const int ldx = gate ? D : J.lda;
+  float4 xv[NQ], yv[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    const int t = ch.row(idx / C4), col = c0 + (idx % C4) * 4;
+    xv[q] = z4;
+    yv[q] = z4;
+    if (t >= 0) {
+      xv[q] = *reinterpret_cast<const float4*>(X + (size_t)t * ldx + col);
+      if (gate) yv[q] = *reinterpret_cast<const float4*>(J.s + (size_t)t * J.lda + col);
+    }
+  }
+  float uv = 0.0f;
+  if (gate) {
+    const int t = ch.row(tid);
+    if (t >= 0) uv = J.A[t];
+  }
+  // chunk p's slots start at row p * (pad + 1): the chunks of a wave's four p on other banks
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int idx = tid + q * GTR_BLOCK;
+    const int slot = idx / C4, o = (slot + (slot >> ch.lg)) * CW + (idx % C4) * 4;
+    *reinterpret_cast<float4*>(S + o) = xv[q];
+    if (gate) *reinterpret_cast<float4*>(S + GTR_SE_YOFF + o) = yv[q];
+  }
+  if (gate) S[GTR_SE_UOFF + tid] = uv;
+  __syncthreads();
+  const int c = tid % CW, p = tid / CW;
+  if (p < P) {
+    constexpr int PH = 16;
+    float s0[PH], s1[PH], s2[PH];
+#pragma unroll
+    for (int ph = 0; ph < PH; ++ph) s0[ph] = s1[ph] = s2[ph] = 0.0f;
+    const int nr = max(0, min(ch.N - p * ch.per, ch.per));
+    const float* Sx = S + ((p << ch.lg) + p) * CW + c;
+    const float* Su = S + GTR_SE_UOFF + (p << ch.lg);
+    for (int r0 = 0; r0 < nr; r0 += PH) {
+#pragma unroll
+      for (int ph = 0; ph < PH; ++ph) {
+        const float x = Sx[(r0 + ph) * CW];
+        if (gate) {
+          const float y = Sx[GTR_SE_YOFF + (r0 + ph) * CW];
+          const float u = Su[r0 + ph];
+          s0[ph] = __builtin_fmaf(u, x, s0[ph]);
+          s1[ph] = __builtin_fmaf(u, y, s1[ph]);
+          s2[ph] = __builtin_fmaf(u, x - y, s2[ph]);
+        } else {
+          s0[ph] += x;
+        }
+      }
+    }
+    float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
+#pragma unroll
+    for (int ph = 0; ph < PH; ++ph) {
+      g0 += s0[ph];
+      g1 += s1[ph];
+      g2 += s2[ph];
+    }
+    cv[0][p][c] = g0;
+    if (gate) {
+      cv[1][p][c] = g1;
+      cv[2][p][c] = g2;
+    }
+  }
+  __syncthreads();
+  if (tid >= nown) return;
+  float g = 0.0f;
+  for (int q = 0; q < P; ++q) g += cv[tid / CW][q][tid % CW];
+  wait();
+  const AdamStep st = s_st;
+  st.apply(pv, mv, vv, g);
+  fp[e] = pv;
+  fm[e] = mv;
+  fv[e] = vv;
+}
+
+template <int D>
+__global__ __launch_bounds__(GTR_TAIL_BLOCK) void k_step_end_small(StepEndK a) {
+  // as k_step_tail<D, true>: a fifth wave computes the step's AdamW scalars while the body
+  // waves issue their loads; every role needs them only right before AdamW
+  __shared__ AdamStep s_st;
+  __shared__ int32_t s_t;
+  __shared__ int s_ready;
+  __shared__ __attribute__((aligned(16))) float s_x[GTR_SE_LDS];
+  __shared__ float s_cv[3][GTR_SE_MAXP][GTR_SE_CW];
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) s_ready = 0;
+  __syncthreads();
+  if (tid >= GTR_BLOCK) {
+    if (tid == GTR_BLOCK) {
+      const int64_t t = *a.opt.step_dev + a.opt.step_offset;
+      s_st.init(a.opt, t);
+      s_t = (int32_t)t;
+      __hip_atomic_store(&s_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      // fused begin: the step's dropout counter.  No workgroup of this launch reads it
+      // (weight gradients, touched rows and gamma / beta use no dropout), so the
+      // increment needs no ordering against the others; keep it that way.
+      if (blk == a.nb_tiles + a.nb_rows && a.tl.rng_inc) *a.tl.rng_inc += 1;
+    }
+    return;
+  }
+  auto wait = [&]() {
+    while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+      __builtin_amdgcn_s_sleep(1);
+  };
+  if (blk < a.nb_tiles) {
+    int jid = 0;
+#pragma unroll
+    for (int i = 1; i < GTR_MAX_WJOBS; ++i) jid += i < a.njobs && blk >= a.blk0s[i] ? 1 : 0;
+    const SEJob& J = a.jobs[jid];
+    const int tile = blk - a.blk0s[jid];
+    if (J.type == WJ_MM)
+      se_mm_tile<GTR_SE_OM, GTR_SE_ON>(J, tile, a.bt.hdr, a.bt.n_cap, a.P, s_x, a.tl.flat, a.tl.flat_m, a.tl.flat_v,
+                                       s_st, wait);
+    else
+      se_col_tile(J, tile, a.bt.hdr, a.bt.n_cap, a.P, a.D, s_x, s_cv, a.tl.flat, a.tl.flat_m, a.tl.flat_v, s_st, wait);
+    return;
+  }
+  if (blk < a.nb_tiles + a.nb_rows) {
+    rows_body<D>((blk - a.nb_tiles) * GTR_BLOCK + tid, a.bt, a.T, a.tl.skeys, a.tl.svals, a.tl.dx0, a.tl.se,
+                 a.tl.coef_tgt, a.tl.coef_neg, a.tl.table, a.tl.table_m, a.tl.table_v, nullptr, s_st,
+                 a.tl.lazy_consts ? a.tl.stamp : nullptr, s_t, wait);
+    return;
+  }
+  // BatchNorm gamma / beta (one partial: bn_gsum) and, in the role's first workgroup, the
+  // loss of the step: k_step_tail's small part on these segments
+  const int sb = blk - a.nb_tiles - a.nb_rows;
+  const bool loss = sb == 0 && a.tl.loss_part;
+  const int lnp = loss ? a.tl.loss_nparts : 0;
+  float2 lp = make_float2(0.f, 0.f);
+  if (tid < lnp) lp = make_float2(a.tl.loss_part[(size_t)tid * 2], a.tl.loss_part[(size_t)tid * 2 + 1]);
+  if (a.nseg > 0) {
+    int sg = 0;
+#pragma unroll
+    for (int i = 1; i < GTR_SE_SEGS; ++i) sg += i < a.nseg && sb >= a.gb0s[i] ? 1 : 0;
+    const gtr_segment& S = a.segs[sg];
+    const int64_t off = (int64_t)(sb - a.gb0s[sg]) * GTR_BLOCK + tid;
+    if (off < S.len) {
+      const int64_t e = S.begin + off;
+      float pv = a.tl.flat[e], mv = a.tl.flat_m[e], vv = a.tl.flat_v[e];
+      float g = 0.0f;
+      for (int q = 0; q < S.nparts; ++q) g += S.src[(int64_t)q * S.pstride + off];
+      wait();
+      const AdamStep st = s_st;
+      st.apply(pv, mv, vv, g);
+      a.tl.flat[e] = pv;
+      a.tl.flat_m[e] = mv;
+      a.tl.flat_v[e] = vv;
+    }
+  }
+  if (loss) {
+    float acc = 0.0f;
+    if (tid < lnp) acc += lp.x + lp.y;
+    for (int q = tid + GTR_BLOCK; q < lnp; q += GTR_BLOCK)
+      acc += a.tl.loss_part[(size_t)q * 2] + a.tl.loss_part[(size_t)q * 2 + 1];
+    s_x[tid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      // (threads past the partial count hold +0: adding them changes nothing, they are skipped)
+      float t = 0.0f;
+      const int nq = lnp < GTR_BLOCK ? lnp : GTR_BLOCK;
+      for (int q = 0; q < nq; ++q) t += s_x[q];
+      a.tl.loss_out[0] = t;
+      if (a.tl.loss_acc) a.tl.loss_acc[0] += (double)t;
+    }
+  } else if (sb == 0 && a.tl.loss_acc && tid == 0) {  // the readout wrote the loss itself
+    a.tl.loss_acc[0] += (double)a.tl.loss_out[0];
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(GTR_BLOCK) void k_scatter_rows(gtr_batch bt, int mode, const float* src,
                                                             const float* coef_tgt, const float* coef_neg,
@@ -2011,6 +2393,122 @@ int gtr_step_tail_wgrad(const gtr_config* cfg, const gtr_batch* bt, const gtr_la
     case 64: hipLaunchKernelGGL(k_step_tail_wgrad<64>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
     case 128: hipLaunchKernelGGL(k_step_tail_wgrad<128>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
     default: hipLaunchKernelGGL(k_step_tail_wgrad<256>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
+  }
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}
+
+// the padded row slots of n_chunks chunks at capacity n_cap (SEChunks at N = n_cap)
+static int step_end_slots(int n_cap, int n_chunks) {
+  const int per = (n_cap + n_chunks - 1) / n_chunks;
+  int pad = 16;
+  while (pad < per) pad *= 2;
+  return n_chunks * pad;
+}
+
+int gtr_step_end_small_fits(int n_cap, int n_chunks, int pe_k) {
+  return n_cap > 0 && n_chunks > 0 && n_chunks <= GTR_SE_MAXP && step_end_slots(n_cap, n_chunks) <= GTR_SE_ROWS &&
+                 pe_k >= 0 && pe_k % 4 == 0
+             ? 1
+             : 0;
+}
+
+int gtr_step_end_small(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* pe_tab,
+                       int n_chunks, const int64_t* layer_flat, const int64_t* pe_flat, int num_items,
+                       const gtr_tail* tail, const gtr_segment* segs, int nseg, const gtr_adam* opt,
+                       gtr_stream_t stream) {
+  if (!cfg || !bt || !layers || !layer_flat || !tail || !opt || !opt->step_dev || num_items <= 0 || nseg < 0 ||
+      nseg > GTR_SE_SEGS || (nseg > 0 && !segs) || !dim_ok(cfg->dim) || n_chunks <= 0 || !bt->hdr ||
+      3 * cfg->num_layers + 1 > GTR_MAX_WJOBS || (cfg->pe_k > 0 && !pe_flat)) {
+    set_error("gtr_step_end_small: bad arguments");
+    return GTR_E_ARG;
+  }
+  const gtr_tail& t = *tail;
+  const int D = cfg->dim;
+  const int m_cap = bt->n_cap + bt->b_cap * (1 + bt->n_neg);
+  if (m_cap > GTR_BEGIN_MCAP || !gtr_step_end_small_fits(bt->n_cap, n_chunks, cfg->pe_k)) {
+    set_error("gtr_step_end_small: batch too large (n_cap %d in %d chunks, m_cap %d, pe_k %d; one staging round holds "
+              "%d row slots): use gtr_wgrad_rows + gtr_step_tail_small",
+              bt->n_cap, n_chunks, m_cap, cfg->pe_k, GTR_SE_ROWS);
+    return GTR_E_ARG;
+  }
+  if (!t.lazy_consts && t.sweep_from < num_items) {
+    set_error("gtr_step_end_small: the untouched-row sweep must run in the chain (sweep_from == num_items)");
+    return GTR_E_ARG;
+  }
+  if (!t.skeys || !t.svals || !t.dx0 || !t.se || !t.coef_tgt || !t.coef_neg || !t.table || !t.table_m ||
+      !t.table_v || !t.stamp || !t.flat || !t.flat_m || !t.flat_v || t.flat_total <= 0 ||
+      (t.loss_part && (!t.loss_out || t.loss_nparts < 0))) {
+    set_error("gtr_step_end_small: missing buffers");
+    return GTR_E_ARG;
+  }
+  StepEndK k{};
+  k.bt = *bt;
+  k.tl = t;
+  k.opt = *opt;
+  k.T = num_items;
+  k.P = n_chunks;
+  k.D = D;
+  WJob wj[GTR_MAX_WJOBS];
+  int nj = 0, unused = 0;
+  if (const int rc = build_wjobs(cfg, bt, layers, t.dx0, pe_tab, nullptr, nullptr, layer_flat, pe_flat, 1, 0,
+                                 cfg->num_layers, wj, nj, unused, false))
+    return rc;
+  constexpr int TM = 16 * GTR_SE_OM, TN = 16 * GTR_SE_ON;
+  auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  int blocks = 0;
+  for (int i = 0; i < nj; ++i) {
+    const WJob& w = wj[i];
+    SEJob& j = k.jobs[i];
+    j = SEJob{};
+    j.type = w.type; j.M1 = w.M1; j.M2 = w.M2; j.lda = w.lda; j.ldb = w.ldb;
+    j.A = w.A; j.B = w.B; j.bidx = w.bidx; j.agg = w.agg; j.s = w.s; j.fW = w.fW; j.fB = w.fB;
+    k.blk0s[i] = blocks;
+    // every row is read as float4 runs; every output must lie inside the flat buffer
+    bool ok;
+    if (w.type == WJ_MM) {
+      j.hasb = w.tn * 64 > w.M2 ? 1 : 0;  // wgrad_tile's tiles reach the ones column at M2
+      j.tn = (w.M2 + j.hasb + TN - 1) / TN;
+      blocks += ((w.M1 + TM - 1) / TM) * j.tn;
+      ok = w.A && w.B && al16(w.A) && al16(w.B) && w.lda % 4 == 0 && w.ldb % 4 == 0 && w.M1 % 4 == 0 &&
+           w.M2 % 4 == 0 && w.fW >= 0 && w.fW + (int64_t)w.M1 * w.M2 <= t.flat_total &&
+           (!j.hasb || (w.fB >= 0 && w.fB + w.M1 <= t.flat_total));
+    } else if (w.type == WJ_COLSUM) {
+      blocks += w.M1 / GTR_SE_CW;
+      ok = w.A && al16(w.A) && w.lda % 4 == 0 && w.M1 % GTR_SE_CW == 0 && w.fB >= 0 && w.fB + w.M1 <= t.flat_total;
+    } else {
+      blocks += D / GTR_SE_CW;
+      ok = w.A && w.agg && w.s && al16(w.agg) && al16(w.s) && w.lda % 4 == 0 && w.fW >= 0 &&
+           w.fW + 3 * (int64_t)D <= t.flat_total;
+    }
+    if (!ok) {
+      set_error("gtr_step_end_small: job %d: a null or misaligned (16 B) operand, or flat offsets outside the buffer", i);
+      return GTR_E_ARG;
+    }
+  }
+  k.njobs = nj;
+  k.nb_tiles = blocks;
+  k.nb_rows = (int)(((int64_t)m_cap * (D / 4) + GTR_BLOCK - 1) / GTR_BLOCK);
+  int gb = 0;
+  for (int i = 0; i < nseg; ++i) {
+    const gtr_segment& s = segs[i];
+    if (s.begin < 0 || s.len < 0 || s.begin + s.len > t.flat_total || !s.src || s.nparts < 0) {
+      set_error("gtr_step_end_small: segment %d outside the flat buffer", i);
+      return GTR_E_ARG;
+    }
+    k.segs[i] = s;
+    k.gb0s[i] = gb;
+    gb += (int)((s.len + GTR_BLOCK - 1) / GTR_BLOCK);
+  }
+  k.nseg = nseg;
+  k.nb_gb = gb > 0 ? gb : 1;  // (the loss sum and the dropout counter need the role's first workgroup)
+  const int grid = k.nb_tiles + k.nb_rows + k.nb_gb;
+  hipStream_t s = (hipStream_t)stream;
+  switch (D) {
+    case 32: hipLaunchKernelGGL(k_step_end_small<32>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    case 64: hipLaunchKernelGGL(k_step_end_small<64>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    case 128: hipLaunchKernelGGL(k_step_end_small<128>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
+    default: hipLaunchKernelGGL(k_step_end_small<256>, dim3(grid), dim3(GTR_TAIL_BLOCK), 0, s, k); break;
   }
   GTR_HIP_CHECK_LAUNCH();
   return GTR_OK;

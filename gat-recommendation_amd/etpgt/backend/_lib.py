@@ -179,6 +179,8 @@ _SIGS = {
                                       C.c_int, P]),
     "gtr_wgrad_rows": (C.c_int, [P, P, P, P, P, P, P, C.c_int, i64, C.c_int, C.c_int, C.c_int, P, P, P]),
     "gtr_step_tail_small": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P]),
+    "gtr_step_end_small": (C.c_int, [P, P, P, P, C.c_int, P, P, C.c_int, P, P, C.c_int, P, P]),
+    "gtr_step_end_small_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gtr_step_begin_lazy": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, P, P, C.c_size_t, P, P]),
     "gtr_lazy_flush": (C.c_int, [C.c_int, C.c_int, P, P, P, P]),
     "gtr_tail_carry_floats": (C.c_int, [C.c_int, C.c_int]),

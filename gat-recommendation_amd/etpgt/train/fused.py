@@ -332,8 +332,26 @@ class FusedTrainStep:
         # walks its 4k elements' partials serially); needs the sweep in the chain or a lazy table
         self.tail_wgrad = (self.dp is None and self.shard is None and m_cap <= 8192
                            and (self.lazy or t.sweep_from >= eng.T) and os.environ.get("GTR_TAILW", "0") == "1")
-        if self.tail_wgrad:
-            self.tile_cnt = torch.zeros(4096, dtype=torch.int32, device=self.dev)
+        # single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
+        # weight-gradient launch (gtr_wgrad_rows -- the rows do not depend on the weight
+        # gradients) and the tail keeps the small parameters (gtr_step_tail_small); bitwise
+        # the two plain launches, GTR_ROWS_EARLY=0 restores them
+        self.rows_early = (self.dp is None and self.shard is None and m_cap <= 8192 and not self.tail_wgrad
+                           and os.environ.get("GTR_ROWS_EARLY", "1") != "0")
+        # ... and where all node rows fit one staging round in LDS (n_cap <= 256 at the default
+        # chunks), that pair is ONE launch whose tiles own their outputs and apply AdamW
+        # themselves (gtr_step_end_small): no slabs, no tail launch; bitwise the pair,
+        # GTR_STEP_END=0 restores it.  Not with FFN blocks (their slabs come from
+        # gtr_ffn_wgrad) and only with the sweep in the chain or a lazy table.  Its sums are
+        # those of the pair's VALU tiles, so it stays off where the pair would run MFMA tiles
+        # (GTR_WGRAD=mfma, or chunks of >= 128 rows under GTR_WGRAD_ROWS).
+        valu = os.environ.get("GTR_WGRAD") != "mfma" and -(-self.caps.n_cap // self.ws.P) < 128
+        self.step_end = (self.rows_early and self.ws.ffns is None and (self.lazy or t.sweep_from >= eng.T) and valu
+                         and bool(L.lib().gtr_step_end_small_fits(self.caps.n_cap, self.ws.P, eng.K))
+                         and os.environ.get("GTR_STEP_END", "1") != "0")
+        if self.tail_wgrad or self.step_end:
+            if self.tail_wgrad:
+                self.tile_cnt = torch.zeros(4096, dtype=torch.int32, device=self.dev)
             lay = eng.flat.layout
             gb = [i for i in range(self.nseg)
                   if any(self.segs[i].begin == lay.seg(f"{l}.{n}").begin for l in range(eng.L) for n in ("gamma", "beta"))]
@@ -344,12 +362,6 @@ class FusedTrainStep:
             self.layer_flat = (C.c_int64 * (3 * eng.L))(*[lay.seg(f"{l}.{n}").begin for l in range(eng.L)
                                                           for n in ("w_all", "b_all", "w_beta")])
             self.pe_flat = (C.c_int64 * 2)(lay.seg("pe.w").begin, lay.seg("pe.b").begin) if eng.K > 0 else None
-        # single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
-        # weight-gradient launch (gtr_wgrad_rows -- the rows do not depend on the weight
-        # gradients) and the tail keeps the small parameters (gtr_step_tail_small); bitwise
-        # the two plain launches, GTR_ROWS_EARLY=0 restores them
-        self.rows_early = (self.dp is None and self.shard is None and m_cap <= 8192 and not self.tail_wgrad
-                           and os.environ.get("GTR_ROWS_EARLY", "1") != "0")
         self.graph = None
         self.graph_pe = None
         self.graph_b = None
@@ -534,7 +546,7 @@ class FusedTrainStep:
         self._begin(bs, st)
         eng.run_forward(ws, cfg, bs, L.RO_FWD | L.RO_LOSS | L.RO_BWD, self.loss_kind, self.temperature, self.alpha,
                         split=self.split)
-        eng.run_backward(ws, cfg, bs, wgrad=not self.tail_wgrad, split=self.split,
+        eng.run_backward(ws, cfg, bs, wgrad=not (self.tail_wgrad or self.step_end), split=self.split,
                          rows=(self.tail, self.adam) if self.rows_early else None)
         if self.dp is not None:
             self.dp.launch_pack(bs, st)
@@ -556,6 +568,12 @@ class FusedTrainStep:
                                                 C.byref(self.tail), self.segs_gb, self.nseg_gb, C.byref(self.adam),
                                                 self.tile_cnt.data_ptr(), self.tile_cnt.numel(), st),
                     "step_tail_wgrad")
+        elif self.step_end:  # weight gradients, touched rows and the small tail: one launch
+            pe = self.model.laplacian_pe._cached_pe if eng.K > 0 else None
+            L.check(L.lib().gtr_step_end_small(C.byref(self.cfg), C.byref(bs), self.ws.structs,
+                                               None if pe is None else pe.data_ptr(), self.ws.P, self.layer_flat,
+                                               self.pe_flat, eng.T, C.byref(self.tail), self.segs_gb, self.nseg_gb,
+                                               C.byref(self.adam), st), "step_end_small")
         elif self.rows_early:  # the touched rows ran beside the weight gradients
             L.check(L.lib().gtr_step_tail_small(C.byref(bs), eng.T, eng.D, C.byref(self.tail), self.segs, self.nseg,
                                                 C.byref(self.adam), st), "step_tail_small")

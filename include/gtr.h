@@ -524,6 +524,29 @@ int gtr_wgrad_rows(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* 
 int gtr_step_tail_small(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail,
                         const gtr_segment* segs, int nseg, const gtr_adam* opt, gtr_stream_t stream);
 
+/* Small batches whose node rows fit one staging round in LDS: gtr_wgrad_rows +
+ * gtr_step_tail_small as ONE launch of independent workgroups, with no slab in between.
+ *   - weight-gradient tiles: every output of the dense jobs (w_all, b_all, w_beta, the
+ *     LapPE projection) is owned by one thread, which forms the n_chunks chunk values over
+ *     the same row ranges with the same operations in the same order as gtr_wgrad's tiles,
+ *     adds them in chunk order from +0 as the tail does with the slabs, and applies AdamW
+ *     to the flat parameter (layer_flat / pe_flat as gtr_step_tail_wgrad);
+ *   - touched rows: as gtr_wgrad_rows;
+ *   - segs (<= 16): the BatchNorm gamma / beta segments (bn_gsum), the loss sum,
+ *     tail->rng_inc and tail->loss_acc as gtr_step_tail_small.
+ * Bit for bit gtr_wgrad_rows + gtr_step_tail_small with the same n_chunks.  Needs
+ * gtr_step_end_small_fits(n_cap, n_chunks, pe_k), m_cap <= 8192, the untouched-row sweep
+ * in the chain or a lazy table, 16-byte aligned activations and no FFN blocks (their
+ * gradients are not among these jobs); GTR_E_ARG otherwise.                            */
+int gtr_step_end_small(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* pe_tab,
+                       int n_chunks, const int64_t* layer_flat, const int64_t* pe_flat, int num_items,
+                       const gtr_tail* tail, const gtr_segment* segs, int nseg, const gtr_adam* opt,
+                       gtr_stream_t stream);
+/* 1: n_chunks row chunks of n_cap node rows, each padded to a power of two >= 16 slots,
+ * fit the 256 row slots of gtr_step_end_small's staging round, n_chunks <= 16 and the
+ * LapPE width is a multiple of 4 (float4 rows).                                        */
+int gtr_step_end_small_fits(int n_cap, int n_chunks, int pe_k);
+
 /* ---- data-parallel step (one process per GPU; etpgt.train.distributed) --------
  * Each rank packs its gradients into `pack` (words per rank = layout.words):
  *   [0, flat_total)          summed small-parameter gradient (flat layout)
