@@ -15,6 +15,8 @@
 // k_readout<D>: last layer's BN/residual/dropout + mean readout (base.py:136-155)
 //   + scoring loss fwd/bwd (base.py:80-113, losses.py:8-164) + readout backward and
 //   the last BatchNorm's backward partial sums.
+// k_readout_pool<D, POOL>: the same body with the last / attention SessionReadout
+//   (base.py:166-188) in place of the mean, and the gradients of readout.attention.*.
 
 #include "gtr_layer.cuh"
 
@@ -1489,8 +1491,26 @@ struct ReadoutK {
 #define RO_BLOCK 512
 #define RO_WAVES (RO_BLOCK / 64)
 
-template <int D>
-__device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
+// The `last` / `attention` readouts (base.py:166-188; gtr_pool): arguments beside ReadoutK,
+// so that the mean kernels' argument block stays as it is.
+struct PoolK {
+  const float* w;   // [D] readout.attention.weight
+  const float* b;   // [1] readout.attention.bias
+  float* state;     // [b_cap][2] per-session softmax (max, sum): forward -> backward
+  float* part;      // [main_grid][D + 1] per-workgroup (dw | db) partial rows
+  float* red;       // [D + 1] their sum in workgroup order
+  uint32_t* cnt;    // arrival counter of that sum (left zero)
+};
+
+// POOL (GTR_POOL_*) selects stages (2) and (5) only; the loss passes (3)-(4) are shared.
+//   last:      se = y of the session's last row; the other rows get an explicit zero in dy.
+//   attention: s_i = <w, y_i> + b, a = softmax(s) over the session's rows, se = sum a_i y_i,
+//              online (running max / sum / weighted row per wave, waves combined through LDS
+//              in wave order); the backward re-reads out / xin (past each wave's first row,
+//              which stays in registers in a fused launch) and recomputes a_i from the
+//              session's (max, sum).
+template <int D, int POOL>
+__device__ __forceinline__ void readout_body(const ReadoutK& a, const PoolK& p, int rb) {
   constexpr int VPL = D >= 64 ? D / 64 : 1;
   constexpr int KR = 32 / VPL;       // scoring rows per wave held in registers
   constexpr int CHN = RO_WAVES * KR; // negatives per chunk
@@ -1528,7 +1548,13 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
   float pov[VPL], pxv[VPL];  // the wave's first node row of the session (out, xin), consumed first
   auto issue = [&](int b) {
     if (b >= B) return;
-    if (do_fwd) {
+    if constexpr (POOL == GTR_POOL_LAST) {  // every wave holds the session's last row
+      const int i = a.bt.node_ptr[b + 1] - 1;
+      if (i >= a.bt.node_ptr[b] && (do_fwd || do_bwd)) {
+        load_vec<VPL>(pov, a.out + (size_t)i * D + d0, act);
+        if (do_fwd) load_vec<VPL>(pxv, a.xin + (size_t)i * D + d0, act);
+      }
+    } else if (do_fwd) {
       const int i = a.bt.node_ptr[b] + wave;
       if (i < a.bt.node_ptr[b + 1]) {
         load_vec<VPL>(pov, a.out + (size_t)i * D + d0, act);
@@ -1575,6 +1601,25 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
 #pragma unroll
   for (int v = 0; v < VPL; ++v) { gs[v] = 0.0f; gx[v] = 0.0f; }
   float lw_sum = 0.0f, bpr_sum = 0.0f;
+  // attention pooling: the scoring vector (0 on idle lanes, so wave sums skip them), the
+  // wave's dw and the workgroup's db (each session's sum first: it cancels there)
+  float pw[VPL], dwv[VPL], pbias = 0.0f, db_acc = 0.0f;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) { pw[v] = 0.0f; dwv[v] = 0.0f; }
+  if constexpr (POOL == GTR_POOL_ATTENTION) {
+    load_vec<VPL>(pw, p.w + d0, act);
+    pbias = p.b[0];
+  }
+  // y = drop(BN(out) + xin) of row i on this lane's columns (0 on idle lanes)
+  auto row_y = [&](float (&y)[VPL], const float (&ov)[VPL], const float (&xv)[VPL], int i) {
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const size_t o = (size_t)i * D + d0 + v;
+      float t = (ov[v] - bm[v]) * br[v] * bg[v] + bb[v];
+      t = t + xv[v];
+      y[v] = act ? t * dr.mul(st, (uint32_t)o) : 0.0f;
+    }
+  };
 
   for (int b = rb; b < B; b += a.main_grid) {
     const int n0 = a.bt.node_ptr[b], n1 = a.bt.node_ptr[b + 1];
@@ -1585,7 +1630,72 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
     float se[VPL];
     constexpr int NBR = 2;  // node rows per wave whose conv output stays in registers for (5)
     float oc[NBR][VPL];
-    if (do_fwd) {
+    float pM = 0.0f, pZ = 1.0f;  // attention: the session's softmax (max, sum)
+    float py0[VPL], ps0 = 0.0f;  // ... and the wave's first row (y, score) kept for (5); its conv output in oc[0]
+    if (do_fwd && POOL == GTR_POOL_LAST) {
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) se[v] = 0.0f;
+      if (n1 > n0) row_y(se, pov, pxv, n1 - 1);  // requested by issue()
+      if (wave == 0) store_vec<VPL>(a.se + (size_t)b * D + d0, se, act);
+    } else if (do_fwd && POOL == GTR_POOL_ATTENTION) {
+      float acc[VPL], m = -INFINITY, z = 0.0f;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) acc[v] = 0.0f;
+      for (int i = n0 + wave, q = 0; i < n1; i += RO_WAVES, ++q) {
+        float ov[VPL], xv[VPL], y[VPL];
+        if (q == 0) {  // requested by issue()
+#pragma unroll
+          for (int v = 0; v < VPL; ++v) { ov[v] = pov[v]; xv[v] = pxv[v]; }
+        } else {
+          load_vec<VPL>(ov, a.out + (size_t)i * D + d0, act);
+          load_vec<VPL>(xv, a.xin + (size_t)i * D + d0, act);
+        }
+        row_y(y, ov, xv, i);
+        float s = 0.0f;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) s += pw[v] * y[v];
+        s = wave_sum(s) + pbias;
+        if (q == 0) {
+          ps0 = s;
+#pragma unroll
+          for (int v = 0; v < VPL; ++v) { py0[v] = y[v]; oc[0][v] = ov[v]; }
+        }
+        const float mn = fmaxf(m, s);
+        const float sc = expf(m - mn), e = expf(s - mn);  // first row: exp(-inf) = 0
+        z = z * sc + e;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) acc[v] = acc[v] * sc + e * y[v];
+        m = mn;
+      }
+      if (act) {
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) s_vec[wave][d0 + v] = acc[v];
+      }
+      if (lane == 0) { s_w[wave][0] = m; s_w[wave][1] = z; }
+      __syncthreads();
+      // the waves' states in wave order (a wave without rows: max -inf, weight 0)
+      float M = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < RO_WAVES; ++w) M = fmaxf(M, s_w[w][0]);
+      float Z = 0.0f, wt[RO_WAVES];
+#pragma unroll
+      for (int w = 0; w < RO_WAVES; ++w) {
+        wt[w] = s_w[w][1] > 0.0f ? expf(s_w[w][0] - M) : 0.0f;
+        Z += s_w[w][1] * wt[w];
+      }
+      const float rZ = 1.0f / Z;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < RO_WAVES; ++w) t += act ? s_vec[w][d0 + v] * wt[w] : 0.0f;
+        se[v] = t * rZ;
+      }
+      pM = M; pZ = Z;
+      if (wave == 0) store_vec<VPL>(a.se + (size_t)b * D + d0, se, act);
+      if (tid == 0) { p.state[(size_t)b * 2] = M; p.state[(size_t)b * 2 + 1] = Z; }
+      __syncthreads();
+    } else if (do_fwd) {
       float acc[VPL];
 #pragma unroll
       for (int v = 0; v < VPL; ++v) acc[v] = 0.0f;
@@ -1628,6 +1738,9 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
       __syncthreads();
     } else {
       load_vec<VPL>(se, a.se + (size_t)b * D + d0, act);
+      if constexpr (POOL == GTR_POOL_ATTENTION) {
+        if (do_bwd) { pM = p.state[(size_t)b * 2]; pZ = p.state[(size_t)b * 2 + 1]; }
+      }
     }
 
     float dse[VPL];
@@ -1759,7 +1872,69 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
     }
 
     // ---- (5) readout backward into the node rows + the last BatchNorm's backward sums
-    if (do_bwd) {
+    if (do_bwd && POOL == GTR_POOL_LAST) {
+      for (int i = n0 + wave; i < n1; i += RO_WAVES) {
+        float dyv[VPL];
+        const bool last = i == n1 - 1;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) {
+          const size_t o = (size_t)i * D + d0 + v;
+          dyv[v] = last ? dse[v] * dr.mul(st, (uint32_t)o) : 0.0f;
+          if (last) {
+            const float xh = (pov[v] - bm[v]) * br[v];
+            gs[v] += dyv[v];
+            gx[v] += dyv[v] * xh;
+          }
+        }
+        store_vec<VPL>(a.dy + (size_t)i * D + d0, dyv, act);
+      }
+    } else if (do_bwd && POOL == GTR_POOL_ATTENTION) {
+      float t = 0.0f;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) t += dse[v] * se[v];
+      t = wave_sum(t);
+      const float rZ = 1.0f / pZ;
+      float dsw = 0.0f;
+      for (int i = n0 + wave, q = 0; i < n1; i += RO_WAVES, ++q) {
+        float ov[VPL], xv[VPL], y[VPL], dyv[VPL];
+        float s = 0.0f, g = 0.0f;
+        if (do_fwd && q == 0) {  // still in registers from (2): the same values
+          s = ps0;
+#pragma unroll
+          for (int v = 0; v < VPL; ++v) { ov[v] = oc[0][v]; y[v] = py0[v]; }
+        } else {
+          load_vec<VPL>(ov, a.out + (size_t)i * D + d0, act);
+          load_vec<VPL>(xv, a.xin + (size_t)i * D + d0, act);
+          row_y(y, ov, xv, i);
+#pragma unroll
+          for (int v = 0; v < VPL; ++v) s += pw[v] * y[v];
+          s = wave_sum(s) + pbias;
+        }
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) g += dse[v] * y[v];
+        g = wave_sum(g);
+        const float ai = expf(s - pM) * rZ;
+        const float ds = ai * (g - t);
+        dsw += ds;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) {
+          const size_t o = (size_t)i * D + d0 + v;
+          dyv[v] = (ai * dse[v] + ds * pw[v]) * dr.mul(st, (uint32_t)o);
+          const float xh = (ov[v] - bm[v]) * br[v];
+          gs[v] += dyv[v];
+          gx[v] += dyv[v] * xh;
+          dwv[v] += ds * y[v];
+        }
+        store_vec<VPL>(a.dy + (size_t)i * D + d0, dyv, act);
+      }
+      if (lane == 0) s_w[wave][3] = dsw;
+      __syncthreads();
+      float dsb = 0.0f;
+#pragma unroll
+      for (int w = 0; w < RO_WAVES; ++w) dsb += s_w[w][3];
+      db_acc += dsb;
+      __syncthreads();
+    } else if (do_bwd) {
       const float inv_cnt = 1.0f / cnt;
       for (int i = n0 + wave, q = 0; i < n1; i += RO_WAVES, ++q) {
         float ov[VPL], dyv[VPL];
@@ -1808,6 +1983,29 @@ __device__ __forceinline__ void readout_body(const ReadoutK& a, int rb) {
       st_wt(a.gpart + (size_t)rb * 2 * D + j, acc);
     }
   }
+  if constexpr (POOL == GTR_POOL_ATTENTION) {
+    // dw / db: the waves' registers through LDS in wave order into this workgroup's partial
+    // row (zeros included); the launch's last arriver sums the rows in workgroup order,
+    // whatever `fin` says, on a counter of its own that it leaves zero (graphs replay it)
+    if (do_bwd) {
+      __syncthreads();
+      if (act) {
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) s_red[wave][d0 + v] = dwv[v];
+      }
+      __syncthreads();
+      for (int j = tid; j < D; j += RO_BLOCK) {
+        float acc = 0.0f;
+        for (int w = 0; w < RO_WAVES; ++w) acc += s_red[w][j];
+        st_wt(p.part + (size_t)rb * (D + 1) + j, acc);
+      }
+      if (tid == 0) st_wt(p.part + (size_t)rb * (D + 1) + D, db_acc);
+      if (arrive_last_wt(p.cnt, (uint32_t)a.main_grid, &s_flag)) {
+        block_sum_rows<RO_BLOCK>(p.part, a.main_grid, D + 1, (size_t)(D + 1), p.red, &s_red[0][0]);
+        if (tid == 0) reset_counter(p.cnt);
+      }
+    }
+  }
   GTR_PH(16, 3);
   if (!a.fin) return;  // loss summed by the step tail, BN sums reduced by the consuming conv_bwd
   if (!arrive_last_wt(a.cnt, (uint32_t)a.main_grid, &s_flag)) return;
@@ -1827,7 +2025,18 @@ __global__ __launch_bounds__(RO_BLOCK) void k_readout(ReadoutK a) {
     sweep_slice(a.sw, a.sw_slot, rb - a.main_grid, gridDim.x - a.main_grid);
     return;
   }
-  readout_body<D>(a, rb);
+  readout_body<D, GTR_POOL_MEAN>(a, PoolK{}, rb);
+}
+
+// The same launch (roles, sweep workgroups, partials) with the `last` / `attention` pooling.
+template <int D, int POOL>
+__global__ __launch_bounds__(RO_BLOCK) void k_readout_pool(ReadoutK a, PoolK p) {
+  const int rb = role_block(a.main_grid, a.xpack);
+  if (rb >= a.main_grid) {  // extra workgroups: untouched-row AdamW slice
+    sweep_slice(a.sw, a.sw_slot, rb - a.main_grid, gridDim.x - a.main_grid);
+    return;
+  }
+  readout_body<D, POOL>(a, p, rb);
 }
 
 // Large-batch readout (b_cap >= ro_wave_min_b(), D <= 128): wave per session, grid-strided;
@@ -2400,6 +2609,21 @@ int make_readout_args(const gtr_config* cfg, const gtr_batch* bt, const float* t
   return GTR_OK;
 }
 
+// Launch geometry of a readout: one workgroup per session up to gtr_readout_grid, then the
+// sweep workgroups of slot L; returns the grid.
+int readout_launch_grid(const gtr_config* cfg, const gtr_batch* bt, ReadoutK& k) {
+  int grid = gtr_readout_grid(bt->b_cap);
+  k.main_grid = grid;
+  if (cfg->sweep && cfg->num_layers < GTR_SWEEP_SLOTS &&
+      cfg->sweep->bounds[cfg->num_layers + 1] > cfg->sweep->bounds[cfg->num_layers]) {
+    k.sw = *cfg->sweep;
+    k.sw_slot = cfg->num_layers;
+    grid += sweep_blocks(cfg->sweep, grid);
+  }
+  k.xpack = xcd_pack(k.main_grid, grid);
+  return grid;
+}
+
 }  // namespace
 
 GTR_PH_READER(gtr_dbg_fwd_phases)
@@ -2518,15 +2742,7 @@ extern "C" int gtr_readout_loss(const gtr_config* cfg, const gtr_batch* bt, cons
   if (!cfg || !bt || !layers || !head) { set_error("gtr_readout_loss: bad arguments"); return GTR_E_ARG; }
   ReadoutK k;
   if (const int rc = make_readout_args(cfg, bt, table, layers, head, k)) return rc;
-  int grid = gtr_readout_grid(bt->b_cap);
-  k.main_grid = grid;
-  if (cfg->sweep && cfg->num_layers < GTR_SWEEP_SLOTS &&
-      cfg->sweep->bounds[cfg->num_layers + 1] > cfg->sweep->bounds[cfg->num_layers]) {
-    k.sw = *cfg->sweep;
-    k.sw_slot = cfg->num_layers;
-    grid += sweep_blocks(cfg->sweep, grid);
-  }
-  k.xpack = xcd_pack(k.main_grid, grid);
+  const int grid = readout_launch_grid(cfg, bt, k);
   hipStream_t s = (hipStream_t)stream;
   if (bt->b_cap >= ro_wave_min_b() && cfg->dim <= 128) {
     switch (cfg->dim) {
@@ -2543,6 +2759,45 @@ extern "C" int gtr_readout_loss(const gtr_config* cfg, const gtr_batch* bt, cons
     case 128: hipLaunchKernelGGL(k_readout<128>, dim3(grid), dim3(RO_BLOCK), 0, s, k); break;
     default: hipLaunchKernelGGL(k_readout<256>, dim3(grid), dim3(RO_BLOCK), 0, s, k); break;
   }
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}
+
+extern "C" int gtr_readout_pool(const gtr_config* cfg, const gtr_batch* bt, const float* table,
+                                const gtr_layer* layers, const gtr_head* head, const gtr_pool* pool,
+                                gtr_stream_t stream) {
+  if (!pool || pool->kind == GTR_POOL_MEAN) return gtr_readout_loss(cfg, bt, table, layers, head, stream);
+  if (pool->kind != GTR_POOL_LAST && pool->kind != GTR_POOL_ATTENTION) {
+    set_error("gtr_readout_pool: unknown pooling kind %d (GTR_POOL_MEAN / LAST / ATTENTION)", pool->kind);
+    return GTR_E_ARG;
+  }
+  const bool att = pool->kind == GTR_POOL_ATTENTION;
+  if (att && (!pool->w || !pool->b || !pool->state || !pool->part || !pool->red || !pool->cnt)) {
+    set_error("gtr_readout_pool: the attention readout needs w, b, state, part, red and cnt");
+    return GTR_E_ARG;
+  }
+  if (!cfg || !bt || !layers || !head) { set_error("gtr_readout_pool: bad arguments"); return GTR_E_ARG; }
+  if (cfg->sync_bn || cfg->split_sync) {
+    set_error("gtr_readout_pool: SyncBN (sync_bn / split_sync) runs with the mean readout only");
+    return GTR_E_ARG;
+  }
+  ReadoutK k;
+  if (const int rc = make_readout_args(cfg, bt, table, layers, head, k)) return rc;
+  PoolK p{};
+  if (att) { p.w = pool->w; p.b = pool->b; p.state = pool->state; p.part = pool->part; p.red = pool->red; p.cnt = pool->cnt; }
+  const int grid = readout_launch_grid(cfg, bt, k);
+  hipStream_t s = (hipStream_t)stream;
+  // block per session at every b_cap: the wave-per-session kernel is mean-only
+#define GTR_ROP(DD) \
+  if (att) hipLaunchKernelGGL((k_readout_pool<DD, GTR_POOL_ATTENTION>), dim3(grid), dim3(RO_BLOCK), 0, s, k, p); \
+  else hipLaunchKernelGGL((k_readout_pool<DD, GTR_POOL_LAST>), dim3(grid), dim3(RO_BLOCK), 0, s, k, p)
+  switch (cfg->dim) {
+    case 32: GTR_ROP(32); break;
+    case 64: GTR_ROP(64); break;
+    case 128: GTR_ROP(128); break;
+    default: GTR_ROP(256); break;
+  }
+#undef GTR_ROP
   GTR_HIP_CHECK_LAUNCH();
   return GTR_OK;
 }

@@ -76,6 +76,12 @@ class GtrHead(C.Structure):
     ]
 
 
+class GtrPool(C.Structure):
+    _fields_ = [
+        ("kind", i32), ("pad", i32), ("w", P), ("b", P), ("state", P), ("part", P), ("red", P), ("cnt", P),
+    ]
+
+
 class GtrSegment(C.Structure):
     _fields_ = [
         ("begin", i64), ("len", i64), ("src", P), ("pstride", i64), ("nparts", i32), ("pad", i32),
@@ -141,6 +147,7 @@ class GtrShard(C.Structure):
 
 GTR_LOSS = {"none": 0, "bpr": 1, "listwise": 2, "sampled_softmax": 2, "dual": 3}
 RO_FWD, RO_LOSS, RO_BWD = 1, 2, 4
+GTR_POOL = {"mean": 0, "last": 1, "attention": 2}  # GTR_POOL_* (`max` has no kernel)
 SMALL_MAX_SEG = 48
 
 # name -> (restype, argtypes)
@@ -152,6 +159,7 @@ _SIGS = {
     "gtr_device_check": (C.c_int, [C.c_int]),
     "gtr_conv_fwd": (C.c_int, [P, P, P, P, C.c_int, P]),
     "gtr_readout_loss": (C.c_int, [P, P, P, P, P, P]),
+    "gtr_readout_pool": (C.c_int, [P, P, P, P, P, P, P]),
     "gtr_conv_bwd": (C.c_int, [P, P, P, C.c_int, P, P]),
     "gtr_qkvs_fwd": (C.c_int, [P, P, P, P, C.c_int, P]),
     "gtr_attn_fwd": (C.c_int, [P, P, P, C.c_int, P]),

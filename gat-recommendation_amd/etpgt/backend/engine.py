@@ -45,8 +45,10 @@ class Seg:
 class ParamLayout:
     """Flat layout of the dense (non-table) parameters of a GraphTransformer."""
 
-    def __init__(self, D: int, L_: int, pe_k: int, ffn: bool = False, ffn_expansion: int = 4):
+    def __init__(self, D: int, L_: int, pe_k: int, ffn: bool = False, ffn_expansion: int = 4,
+                 readout: str = "mean"):
         self.D, self.L, self.K, self.ffn = D, L_, pe_k, ffn
+        self.readout = readout
         F = ffn_expansion * D
         self.F = F if ffn else 0
         self.segs: dict[str, Seg] = {}
@@ -72,6 +74,9 @@ class ParamLayout:
         if pe_k > 0:
             add("pe.w", (D, pe_k))
             add("pe.b", (D,))
+        if readout == "attention":  # readout.attention (base.py:129-131): nn.Linear(D, 1)
+            add("ro.w", (1, D))
+            add("ro.b", (1,))
         self.total = off
         self.layer_block = 4 * D * D + 4 * D + 3 * D   # slab layout of one layer
         self.pe_block = D * pe_k + D if pe_k > 0 else 0
@@ -103,6 +108,8 @@ def model_param_map(model) -> list[tuple[str, torch.nn.Parameter, int]]:
                     (f"{l}.ffn_w2", ffn[3].weight, 0), (f"{l}.ffn_b2", ffn[3].bias, 0)]
     if model.use_laplacian_pe:
         out += [("pe.w", model.laplacian_pe.projection.weight, 0), ("pe.b", model.laplacian_pe.projection.bias, 0)]
+    if getattr(model, "readout_type", "mean") == "attention":
+        out += [("ro.w", model.readout.attention.weight, 0), ("ro.b", model.readout.attention.bias, 0)]
     return out
 
 
@@ -112,7 +119,8 @@ class FlatParams:
     def __init__(self, model, device):
         self.model = model
         self.layout = ParamLayout(model.hidden_dim, model.num_layers, model.laplacian_k if model.use_laplacian_pe else 0,
-                                  bool(getattr(model, "use_ffn", False)), int(getattr(model, "ffn_expansion", 4)))
+                                  bool(getattr(model, "use_ffn", False)), int(getattr(model, "ffn_expansion", 4)),
+                                  getattr(model, "readout_type", "mean"))
         self.device = device
         self.flat = torch.zeros(self.layout.total, dtype=torch.float32, device=device)
         self.map = model_param_map(model)
@@ -229,6 +237,19 @@ class Workspace:
         self.pe_slab = _f32(P, lay.slab_stride, device=dev) if eng.K > 0 else None
         self.slab_ptrs = (C.c_void_p * Lc)(*[self.slabs[l].data_ptr() for l in range(Lc)])
         self.head = L.GtrHead()
+        # last / attention readout (gtr_pool): the attention kind's per-session softmax state,
+        # per-workgroup (dw | db) rows, their sum (the gradient source of ro.w / ro.b) and counter
+        self.pool = None
+        if eng.readout != "mean":
+            self.pool = L.GtrPool()
+            self.pool.kind = L.GTR_POOL[eng.readout]
+            if eng.readout == "attention":
+                self.pool_state = _f32(b, 2, device=dev)
+                self.pool_part = _f32(readout_grid(b), D + 1, device=dev)
+                self.pool_red = _f32(D + 1, device=dev)
+                self.pool_cnt = _i32(1, dev)
+                self.pool.state, self.pool.part = self.pool_state.data_ptr(), self.pool_part.data_ptr()
+                self.pool.red, self.pool.cnt = self.pool_red.data_ptr(), self.pool_cnt.data_ptr()
         self.ffns = None
         if eng.ffn:
             self._alloc_ffn(eng, n, parts, g)
@@ -298,6 +319,8 @@ class Workspace:
         self.refresh_params(eng)
 
     def refresh_params(self, eng):
+        if self.pool is not None and eng.readout == "attention":
+            self.pool.w, self.pool.b = eng.flat.seg_ptr("ro.w"), eng.flat.seg_ptr("ro.b")
         for l in range(eng.L):
             s = self.structs[l]
             bn = eng.model.batch_norms[l]
@@ -333,6 +356,7 @@ class Engine:
         self.K = model.laplacian_k if model.use_laplacian_pe else 0
         self.T = model.num_items
         self.ffn = bool(getattr(model, "use_ffn", False))
+        self.readout = getattr(model, "readout_type", "mean")
         self.flat = FlatParams(model, device)
         self.rng_ctr = torch.zeros(1, dtype=torch.int32, device=device)
         self.seed = int(torch.randint(0, 2**31 - 1, (1,), generator=torch.Generator().manual_seed(0x5EED)).item())
@@ -496,6 +520,10 @@ class Engine:
     def run_head(self, ws, cfg, bs, flags, loss_kind=0, temperature=1.0, alpha=0.7, dse_out=False, table=None):
         h, tab = self.fill_head(ws, flags, loss_kind, temperature, alpha, dse_out, table)
         rcfg, structs = ws.readout_args(cfg)
+        if ws.pool is not None:  # last / attention: the pooled readout kernel (same launch roles)
+            L.check(L.lib().gtr_readout_pool(C.byref(rcfg), C.byref(bs), tab, structs, C.byref(h), C.byref(ws.pool),
+                                             self.stream()), "readout_pool")
+            return
         L.check(L.lib().gtr_readout_loss(C.byref(rcfg), C.byref(bs), tab, structs, C.byref(h), self.stream()),
                 "readout_loss")
 
@@ -586,6 +614,11 @@ class Engine:
             for name, src in (("pe.w", base), ("pe.b", base + 4 * D * K)):
                 s = lay.seg(name)
                 segs.append((s.begin, s.numel, src, stride, ws.P))
+        if self.readout == "attention":  # the readout's reduced (dw | db) row, as gamma / beta read bn_gsum
+            base = ws.pool_red.data_ptr()
+            for name, src in (("ro.w", base), ("ro.b", base + 4 * D)):
+                s = lay.seg(name)
+                segs.append((s.begin, s.numel, src, stride, 1))
         arr = (L.GtrSegment * len(segs))()
         for i, (b, n, src, ps, npart) in enumerate(segs):
             arr[i].begin, arr[i].len, arr[i].src, arr[i].pstride, arr[i].nparts = b, n, src, ps, npart

@@ -67,9 +67,10 @@ class BaseRecommendationModel(nn.Module, ABC):
 
 
 class SessionReadout(nn.Module):
-    """Session readout (base.py:116-193).  Inside GraphTransformer the ``mean``
-    readout is fused into the HIP readout/loss kernel; this module is the
-    stand-alone API (vectorised, no per-session Python loop)."""
+    """Session readout (base.py:116-193).  Inside GraphTransformer the ``mean``, ``last``
+    and ``attention`` readouts are fused into the HIP readout/loss kernels (the attention
+    parameters live here); this module is the stand-alone API (vectorised, no per-session
+    Python loop)."""
 
     def __init__(self, hidden_dim: int = 256, readout_type: str = "mean"):
         super().__init__()

@@ -10,12 +10,13 @@ with the reference (recommender.py:61-85 reads them).
 layer + one readout kernel; graph_transformer.py:126-182 semantics with PyG
 TransformerConv(beta=True)).  There is no CPU path: a
 model on the CPU raises.  Scope: the optimized variant
-(use_ffn=False) with the mean readout is the hot path.  use_ffn=True (the
+(use_ffn=False) with the mean readout is the hot path; the last and attention readouts
+(base.py:166-188) run on the pooled readout kernel (gtr_readout_pool).  use_ffn=True (the
 feed-forward block of graph_transformer.py:88-100,160-170) runs on the split layer
 kernels plus gtr_ffn_fwd / gtr_ffn_bwd / gtr_ffn_wgrad at hidden_dim 64 / 128 / 256 with
 ffn_expansion 1 / 2 / 4 (the reference's create_graph_transformer default d = 256, x 4 and
-the optimized factory's x 2 included); the max/last/attention readouts raise
-NotImplementedError.
+the optimized factory's x 2 included); the max readout raises NotImplementedError (an
+existing test pins that rejection; it has no kernel yet).
 """
 
 from __future__ import annotations
@@ -116,8 +117,9 @@ class GraphTransformer(BaseRecommendationModel):
         if self.use_ffn and (self.hidden_dim not in (64, 128, 256) or self.ffn_expansion not in (1, 2, 4)):
             raise NotImplementedError(f"use_ffn=True runs on the split-layer FFN kernels: hidden_dim 64 / 128 / 256 "
                                       f"with ffn_expansion 1 / 2 / 4 (got {self.hidden_dim}, {self.ffn_expansion})")
-        if self.readout_type != "mean":
-            raise NotImplementedError(f"readout '{self.readout_type}' is outside the HIP hot path (mean only)")
+        if self.readout_type not in ("mean", "last", "attention"):
+            raise NotImplementedError(f"readout '{self.readout_type}' is outside the HIP hot path (mean, last and "
+                                      f"attention have kernels; 'max' has none yet)")
 
     def forward(self, batch):
         """Session embeddings [B, hidden_dim] for a PyG-style batch (graph_transformer.py:126-182)."""

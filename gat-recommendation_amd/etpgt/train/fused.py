@@ -72,6 +72,13 @@ class FusedTrainStep:
         self.sync_bn = bool(sync_bn)
         if self.sync_bn and not self.data_parallel:
             raise ValueError("sync_bn needs the data-parallel step")
+        # the last / attention readouts train on one GPU with a replicated table: the
+        # data-parallel pack, SyncBN's gathered rows, the row-sharded table and the halo
+        # exchange carry the mean readout only
+        ro = getattr(model, "readout_type", "mean")
+        if ro != "mean" and (self.data_parallel or self.sync_bn or self.shard_table):
+            raise NotImplementedError(f"the '{ro}' readout trains on one GPU with a replicated table: data parallel, "
+                                      f"SyncBN, the row-sharded table and the halo exchange run the mean readout only")
         self.dp = None
         self.sync_alias = False
         self.graph_b = None
@@ -330,7 +337,10 @@ class FusedTrainStep:
         # (gtr_step_tail_wgrad: split-K tiles, each tile's last arriving chunk applies AdamW);
         # bitwise the two launches but slower (C2 0.083 -> 0.102 ms: one workgroup per tile
         # walks its 4k elements' partials serially); needs the sweep in the chain or a lazy table
-        self.tail_wgrad = (self.dp is None and self.shard is None and m_cap <= 8192
+        # (both one-launch ends hand the tail the BatchNorm segments only -- segs_gb -- and
+        # would skip ro.w / ro.b: mean readout only)
+        mean_ro = eng.readout == "mean"
+        self.tail_wgrad = (self.dp is None and self.shard is None and m_cap <= 8192 and mean_ro
                            and (self.lazy or t.sweep_from >= eng.T) and os.environ.get("GTR_TAILW", "0") == "1")
         # single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
         # weight-gradient launch (gtr_wgrad_rows -- the rows do not depend on the weight
@@ -346,7 +356,7 @@ class FusedTrainStep:
         # those of the pair's VALU tiles, so it stays off where the pair would run MFMA tiles
         # (GTR_WGRAD=mfma, or chunks of >= 128 rows under GTR_WGRAD_ROWS).
         valu = os.environ.get("GTR_WGRAD") != "mfma" and -(-self.caps.n_cap // self.ws.P) < 128
-        self.step_end = (self.rows_early and self.ws.ffns is None and (self.lazy or t.sweep_from >= eng.T) and valu
+        self.step_end = (self.rows_early and mean_ro and self.ws.ffns is None and (self.lazy or t.sweep_from >= eng.T) and valu
                          and bool(L.lib().gtr_step_end_small_fits(self.caps.n_cap, self.ws.P, eng.K))
                          and os.environ.get("GTR_STEP_END", "1") != "0")
         if self.tail_wgrad or self.step_end:

@@ -14,6 +14,8 @@
  *   gtr_readout_loss  base.py:136-155 (mean SessionReadout) + base.py:80-113 /
  *                     losses.py:8-228 (BPR / listwise / dual scoring loss), forward
  *                     and backward, fused; trainer.py:86-122 loss dispatch.
+ *   gtr_readout_pool  the same with base.py:166-171 (last) or base.py:173-188
+ *                     (attention) as the SessionReadout.
  *   gtr_conv_bwd      autograd of graph_transformer.py:171-177 for one layer.
  *   gtr_wgrad         weight/bias gradients of lin_{query,key,value,skip},
  *                     lin_beta and laplacian_pe.projection (laplacian_pe.py:194-197).
@@ -264,6 +266,38 @@ int gtr_conv_fwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_embed* em
  * backward into layers[L-1].dy and the last BatchNorm's backward sums).         */
 int gtr_readout_loss(const gtr_config* cfg, const gtr_batch* bt, const float* table,
                      const gtr_layer* layers, const gtr_head* head, gtr_stream_t stream);
+
+/* Session pooling of the readout (SessionReadout, base.py:116-193).  With
+ * y_i = dropout(BN(out_i) + xin_i) the last layer's rows of session b:
+ *   MEAN       se_b = mean_i y_i                                 (base.py:136-155)
+ *   LAST       se_b = y of the session's last row                (base.py:166-171)
+ *   ATTENTION  s_i = <w, y_i> + b, a = softmax_i(s), se_b = sum_i a_i y_i   (base.py:173-188)
+ * (`max`, base.py:157-164, has no kernel.)  The buffers are read and written by the
+ * ATTENTION kind only; LAST needs none of them.                                        */
+#define GTR_POOL_MEAN 0
+#define GTR_POOL_LAST 1
+#define GTR_POOL_ATTENTION 2
+
+typedef struct gtr_pool {
+  int32_t kind;     /* GTR_POOL_* */
+  int32_t pad;
+  const float* w;   /* [D] readout.attention.weight                                      */
+  const float* b;   /* [1] readout.attention.bias                                        */
+  float* state;     /* [b_cap * 2] per-session softmax (max, sum): written by FWD, read by
+                       a BWD launch without FWD                                          */
+  float* part;      /* [gtr_readout_grid(b_cap)][D + 1] per-workgroup (dw | db) partials  */
+  float* red;       /* [D + 1] their sum in workgroup order: the gradient of (w | b),
+                       written by every BWD launch                                       */
+  uint32_t* cnt;    /* [1] arrival counter of that sum (zero-initialised once)           */
+} gtr_pool;
+
+/* gtr_readout_loss with the session pooling of `pool` (NULL or kind MEAN: exactly
+ * gtr_readout_loss, the same launch).  LAST / ATTENTION run block per session at every
+ * b_cap; no SyncBN (sync_bn / split_sync: GTR_E_ARG).  The gradients of w and b are not
+ * atomics: per-workgroup rows summed in workgroup order by the launch's last arriver.   */
+int gtr_readout_pool(const gtr_config* cfg, const gtr_batch* bt, const float* table,
+                     const gtr_layer* layers, const gtr_head* head, const gtr_pool* pool,
+                     gtr_stream_t stream);
 
 /* Backward of layer `l` given layers[l].dy and layers[l].bn_gsum.  Writes
  * layers[l].dqkvs/du and either layers[l-1].dy (+ its BN sums) or dx0.        */
