@@ -107,6 +107,20 @@ class GtrTail(C.Structure):
 
 SWEEP_SLOTS = 8
 ABI_VERSION = 9  # GTR_ABI_VERSION of include/gtr.h
+# the weight-gradient launch's job table (GTR_MAX_WJOBS of csrc/gtr_wgrad.cuh) holds three
+# jobs per layer and one for the LapPE projection: training stops at 5 layers, inference
+# (no weight gradients) does not
+MAX_WJOBS = 16
+MAX_TRAIN_LAYERS = (MAX_WJOBS - 1) // 3
+
+
+def check_train_layers(num_layers: int, what: str) -> None:
+    """Refuse a training entry point past the job-table limit, before any device work."""
+    if num_layers > MAX_TRAIN_LAYERS:
+        raise NotImplementedError(
+            f"{what}: training supports at most {MAX_TRAIN_LAYERS} layers (the weight-gradient job table holds "
+            f"{MAX_WJOBS} jobs, three per layer and one for the LapPE projection); this model has {num_layers}. "
+            f"Inference runs at any depth.")
 
 
 class GtrLazy(C.Structure):

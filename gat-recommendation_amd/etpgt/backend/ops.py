@@ -232,6 +232,9 @@ class GraphTransformerFn(torch.autograd.Function):
         if ctx.eng is None:
             raise RuntimeError("backward through the GraphTransformer requires train() mode "
                                "(BatchNorm batch statistics) and grad mode at forward time")
+        # the weight-gradient launch at the end of this path holds at most MAX_TRAIN_LAYERS
+        # layers' jobs: refused before the readout / layer backward kernels are launched
+        L.check_train_layers(ctx.eng.L, "GraphTransformer backward")
         eng, ws, cfg, bs, B = ctx.eng, ctx.ws, ctx.cfg, ctx.bs, ctx.B
         ws.dse_in[:B].copy_(dse)
         eng.run_head(ws, cfg, bs, L.RO_BWD)

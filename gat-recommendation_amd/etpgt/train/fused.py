@@ -37,6 +37,9 @@ class FusedTrainStep:
                  lazy: bool = False, sync_bn: bool = False, lagged: bool = False, shard_table: bool = False):
         if loss not in ("bpr", "listwise", "dual", "sampled_softmax"):
             raise ValueError(f"Unknown loss type: {loss}")
+        # past the weight-gradient job table the step used to fail inside its first run
+        # ("too many layers"): refused here, before the engine binds or anything is captured
+        L.check_train_layers(int(model.num_layers), "FusedTrainStep")
         if getattr(model, "use_ffn", False):
             # the FFN variant trains data parallel (replicated or row-sharded table), with or
             # without SyncBN; SyncBN folds the gathered rows in the FFN's first GEMM (dim 64 / 128,

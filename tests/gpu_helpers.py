@@ -66,6 +66,48 @@ def long_session_batch(n_neg=5, T=300) -> SessionBatch:
     return collate_sessions(out)
 
 
+def capacity_batch(n, e, n_neg=5, T=300, short=3) -> SessionBatch:
+    """Session 0: ``n`` nodes (distinct items) and exactly ``e`` edges in a regular in-degree
+    pattern -- node j receives e // n in-edges (one more for the first e % n nodes) from
+    nodes j, j+1, ... (mod n), so no edge repeats -- followed by ``short`` four-node
+    sessions.  With n >= the row-group width, row group 0 holds session 0 alone: a group of
+    exactly n rows and e edges (group0_geometry reads that back from the packed image)."""
+    deg, extra = divmod(e, n)
+    assert deg + (1 if extra else 0) <= n and n + 4 * short < T, (n, e)
+    rng = np.random.default_rng(2)
+    items = []
+    xs = rng.choice(np.arange(1, T), size=n, replace=False)
+    src, dst = [], []
+    for j in range(n):
+        for k in range(deg + (1 if j < extra else 0)):
+            src.append((j + k) % n); dst.append(j)
+    assert len(src) == e
+    items.append({"x": xs, "edge_index": [src, dst]})
+    for _ in range(short):
+        xs = rng.choice(np.arange(1, T), size=4, replace=False)
+        items.append({"x": xs, "edge_index": [[0, 1, 2, 3, 1], [1, 2, 3, 0, 1]]})
+    out = []
+    for it in items:
+        x = np.asarray(it["x"], np.int64)
+        seen = set(x.tolist())
+        negs = [v for v in rng.integers(1, T, size=8 * n_neg) if int(v) not in seen][:n_neg]
+        assert len(negs) == n_neg
+        out.append({"x": x, "edge_index": np.array(it["edge_index"], np.int64).reshape(2, -1),
+                    "target_item": int(rng.integers(1, T)), "negative_items": np.array(negs, np.int64)})
+    return collate_sessions(out)
+
+
+def group0_geometry(sb: SessionBatch) -> tuple[int, int]:
+    """(rows, edges) of row group 0 as the layer kernels will see them: grp_row / grp_edge
+    read back from the batch's packed image."""
+    from etpgt.data.batch import blob_layout
+
+    caps, blob = sb.packed()
+    lay = blob_layout(caps)
+    gr, ge = lay["grp_row"][0], lay["grp_edge"][0]
+    return int(blob[gr + 1] - blob[gr]), int(blob[ge + 1] - blob[ge])
+
+
 def make_pair(T, D, H, L=2, K=0, dropout=0.0, seed=0, pe_table=None):
     """HIP model (cuda) + oracle model (cpu) with identical parameters."""
     torch.manual_seed(seed)
@@ -236,6 +278,96 @@ class OracleTrio:
         p64 = dict(self.ref64.named_parameters())
         for n, p in self.ref.named_parameters():
             close_trained(hip_params[n], p, p64[n], self.noise[n], 2 * lr * self.steps, prefix + n, p1[n])
+
+
+def eval_vs_oracle(m, ref, sbs, name="se"):
+    """Eval-mode forward (running statistics set to non-trivial values on both sides):
+    session embeddings of every batch against the oracle at 1e-3."""
+    with torch.no_grad():
+        for bn, rbn in zip(m.batch_norms, ref.batch_norms):
+            bn.running_mean.uniform_(-0.1, 0.1)
+            bn.running_var.uniform_(0.5, 2.0)
+            rbn.running_mean.copy_(bn.running_mean.cpu())
+            rbn.running_var.copy_(bn.running_var.cpu())
+    m.eval(); ref.eval()
+    for i, sb in enumerate(sbs):
+        with torch.no_grad():
+            se = m(sb.to("cuda"))
+            se_ref = ref(ref_batch(sb))
+        assert_close(se, se_ref, name=f"{name} (batch {i})")
+
+
+def grads_vs_oracle(m, ref, sb, loss="model_bpr", masks=None, stats=True, name=""):
+    """One train-mode step through autograd (batch BatchNorm statistics; dropout 0, or the
+    oracle applying ``masks``): loss, session embeddings, every parameter gradient (dense
+    table gradient included) and the BatchNorm running statistics -- the bars of
+    test_gpu_parity.test_train_grads (1e-3; gradients 2e-3 with a floor of 1e-6 of the
+    largest gradient entry)."""
+    from etpgt.train.losses import create_loss_function
+
+    m.train(); ref.train()
+    dsb = sb.to("cuda")
+    B = sb.num_graphs
+    n = int(sb.negative_items.numel()) // B
+    se = m(dsb)
+    ref.drop_masks = masks
+    rb = ref_batch(sb)
+    se_ref = ref(rb)
+    ref.drop_masks = None
+    neg = dsb.negative_items.view(B, n)
+    if loss == "model_bpr":
+        L_hip = m.compute_loss(se, dsb.target_item, neg)
+    else:
+        out = create_loss_function(loss, alpha=0.7, temperature=0.5)(se, dsb.target_item, neg, m.item_embedding)
+        L_hip = out[0] if isinstance(out, tuple) else out
+    kind = "bpr" if loss == "model_bpr" else loss
+    L_ref = R.ref_loss(kind, se_ref, rb.target_item, rb.negative_items.view(B, n), ref.item_embedding, 0.7, 0.5)
+    m.zero_grad()
+    L_hip.backward()
+    ref.zero_grad()
+    L_ref.backward()
+    assert_close(se, se_ref, name=f"{name}se")
+    assert_close(L_hip.reshape(1), L_ref.reshape(1), name=f"{name}loss")
+    hp = dict(m.named_parameters())
+    gscale = max(float(p.grad.abs().max()) for p in ref.parameters())
+    for pn, p in ref.named_parameters():
+        assert hp[pn].grad is not None, pn
+        assert_close(hp[pn].grad, p.grad, rtol=2e-3, name=f"{name}grad {pn}", floor=1e-6 * gscale)
+    if stats:
+        hb = dict(m.named_buffers())
+        for bn_, b in ref.named_buffers():
+            if "running" in bn_:
+                assert_close(hb[bn_], b, name=f"{name}{bn_}")
+
+
+def fused_vs_trio(data, D, H, K=0, L=2, loss="bpr", B=32, steps=3, seed=4, lr=1e-3, wd=1e-2):
+    """``steps`` fused steps (FusedTrainStep: graph replay, AdamW) against OracleTrio, as
+    test_gpu_parity._fused_vs_reference: losses at 2e-3, every trained parameter and the
+    running statistics elementwise (close_trained).  Returns the fused step, so the caller
+    can assert the path it took (step_end, ws.split)."""
+    from etpgt.train.fused import FusedTrainStep
+
+    n = 5 if loss != "listwise" else 100
+    m, ref = make_pair(data.table_rows, D, H, L=L, K=K, seed=seed)
+    m.train(); ref.train()
+    fused = FusedTrainStep(m, lr=lr, weight_decay=wd, decoupled=True, loss=loss, temperature=1.0, alpha=0.7)
+    trio = OracleTrio(ref, lambda ps: torch.optim.AdamW(ps, lr=lr, weight_decay=wd))
+    bl = batches(data, B, n, steps, seed=11)
+    losses, rlosses = [], []
+    for sb in bl:
+        losses.append(float(fused(sb.to("cuda"))))
+        rb = ref_batch(sb)
+        rlosses.append(float(trio.step(lambda mod, o: R.ref_train_step(mod, rb, o, loss))))
+    np.testing.assert_allclose(losses, rlosses, rtol=2e-3)
+    fused.flush()
+    trio.compare(dict(m.named_parameters()), lr=lr)
+    b64, b1 = dict(trio.ref64.named_buffers()), dict(trio.ref1.named_buffers())
+    hb = dict(m.named_buffers())
+    for name, b in ref.named_buffers():
+        if "running" in name:
+            close_trained(hb[name], b, b64[name], torch.zeros_like(b, dtype=torch.bool), 0.0, name, b1[name])
+    assert int(hb["batch_norms.0.num_batches_tracked"]) == len(bl)
+    return fused
 
 
 def collect(q, procs, n, timeout=400.0):
