@@ -2581,7 +2581,7 @@ int make_readout_args(const gtr_config* cfg, const gtr_batch* bt, const float* t
   k.loss_kind = head->loss_kind;
   k.cred = cfg->consumer_reduce;
   // finalise in-kernel unless a consumer takes over: the BN sums go to conv_bwd and the
-  // loss to gtr_step_end in the fused step; a loss-only call always finalises itself.
+  // loss to the step tail in the fused step; a loss-only call always finalises itself.
   k.fin = (!cfg->consumer_reduce || !(head->flags & GTR_RO_BWD) || cfg->split_sync) ? 1 : 0;
   k.temperature = head->temperature;
   k.dual_alpha = head->dual_alpha;

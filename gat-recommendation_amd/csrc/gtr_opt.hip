@@ -685,139 +685,6 @@ __global__ __launch_bounds__(DEFER ? GTR_TAIL_BLOCK : GTR_BLOCK) __attribute__((
              reinterpret_cast<float4*>(a.tl.table_v), st, a.vbegin);
 }
 
-// ---- small batches: the weight gradients and the optimizer tail in ONE launch ----------
-// Workgroups: [weight-gradient tile chunks | touched rows | BatchNorm gamma / beta + loss].
-// Each (tile, row chunk) workgroup computes its split-K partial slab exactly as k_wgrad
-// does and records the slab indices it wrote in LDS; the tile's P-th arriving chunk
-// (agent-scope last-arriver election) then sums the P partials of each of those indices in
-// chunk order -- the sum the tail's small-parameter part takes -- and applies AdamW to the
-// flat parameter.  Touched rows and the bn_gsum segments depend only on the backward, so
-// they run beside the tiles.  One launch less on the step's chain, bitwise equal to
-// gtr_wgrad + gtr_step_tail (trainer.py:123-127: backward + optimizer.step()).
-#define GTR_TAILW_SEGS 16
-#define GTR_WT_LIST 4352  // slab indices one tile writes: <= 64 x 64 W + 64 bias, or 64 x (K + 1)
-struct TailWK {
-  gtr_batch bt;
-  gtr_tail tl;
-  gtr_adam opt;
-  int T, nb_rows, nb_wg, nb_small, njobs, D, nseg, P;
-  int64_t stride;
-  int small_total, pad0;
-  uint32_t* cnt;  // one arrival counter per tile (zero between launches)
-  gtr_segment segs[GTR_TAILW_SEGS];
-  WJob jobs[GTR_MAX_WJOBS];
-};
-
-template <int D>
-__global__ __launch_bounds__(GTR_BLOCK) void k_step_tail_wgrad(TailWK a) {
-  __shared__ AdamStep s_st;
-  __shared__ int32_t s_t;
-  __shared__ float s_acc[GTR_BLOCK];
-  __shared__ uint32_t s_list[GTR_WT_LIST];
-  __shared__ int s_n;
-  __shared__ int s_flag;
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    const int64_t t = *a.opt.step_dev + a.opt.step_offset;
-    s_st.init(a.opt, t);
-    s_t = (int32_t)t;
-    s_n = 0;
-  }
-  __syncthreads();
-  const AdamStep st = s_st;
-  int blk = blockIdx.x;
-  if (blk == 0 && tid == 0 && a.tl.rng_inc) *a.tl.rng_inc += 1;  // fused begin: the step's dropout counter
-  if (blk < a.nb_wg) {
-    int jid = 0;
-    while (jid + 1 < a.njobs && blk >= a.jobs[jid + 1].blk0) ++jid;
-    const WJob& J = a.jobs[jid];
-    const int local = blk - J.blk0;
-    const int tile = local / a.P, p = local - tile * a.P;
-    const int N = a.bt.hdr[0];
-    const int per = (N + a.P - 1) / a.P;
-    const int t0 = p * per, t1 = min(N, t0 + per);
-    const int64_t so = (int64_t)p * a.stride;
-    // slab index codes: bits 31..30 = 0 W element, 1 bias element, 2 four W elements
-    auto rec = [&](uint32_t code) { s_list[atomicAdd(&s_n, 1)] = code; };
-    auto emit = [&](int which, int64_t idx, float v) {
-      if (which == 0) J.outW[so + idx] = v;
-      else J.outB[so + idx] = v;
-      rec(((uint32_t)which << 30) | (uint32_t)idx);
-    };
-    auto emit4 = [&](int64_t idx, float4 v) {
-      *reinterpret_cast<float4*>(J.outW + so + idx) = v;
-      rec((2u << 30) | (uint32_t)idx);
-    };
-    if (J.mfma == 1) wgrad_tile_mfma<false>(J, tile, t0, t1, emit, emit4);
-    else if (J.mfma == 2) wgrad_tile_mfma<true>(J, tile, t0, t1, emit, emit4);
-    else wgrad_tile(J, tile, t0, t1, a.D, emit);
-    if (!arrive_last(a.cnt + J.tile0 + tile, (uint32_t)a.P, &s_flag)) return;
-    const int n = s_n;
-    float* P = a.tl.flat;
-    float* M = a.tl.flat_m;
-    float* V = a.tl.flat_v;
-    for (int k = tid; k < n; k += GTR_BLOCK) {
-      const uint32_t code = s_list[k];
-      const uint32_t kind = code >> 30;
-      const int64_t idx = code & 0x3FFFFFFFu;
-      const float* src = kind == 1 ? J.outB : J.outW;
-      const int64_t f0 = kind == 1 ? J.fB : J.fW;
-      const int cnt = kind == 2 ? 4 : 1;
-      for (int c = 0; c < cnt; ++c) {
-        float g = 0.0f;
-        for (int q = 0; q < a.P; ++q) g += src[(int64_t)q * a.stride + idx + c];
-        const int64_t e = f0 + idx + c;
-        float pv = P[e], mv = M[e], vv = V[e];
-        st.apply(pv, mv, vv, g);
-        P[e] = pv;
-        M[e] = mv;
-        V[e] = vv;
-      }
-    }
-    if (tid == 0) reset_counter(a.cnt + J.tile0 + tile);
-    return;
-  }
-  blk -= a.nb_wg;
-  if (blk < a.nb_rows) {
-    rows_body<D>(blk * GTR_BLOCK + tid, a.bt, a.T, a.tl.skeys, a.tl.svals, a.tl.dx0, a.tl.se, a.tl.coef_tgt,
-                 a.tl.coef_neg, a.tl.table, a.tl.table_m, a.tl.table_v, nullptr, st,
-                 a.tl.lazy_consts ? a.tl.stamp : nullptr, s_t);
-    return;
-  }
-  blk -= a.nb_rows;
-  if (blk < a.nb_small) {
-    int64_t i = (int64_t)blk * GTR_BLOCK + tid;  // index into the concatenated segments
-    if (i < a.small_total) {
-      int sg = 0;
-      while (i >= a.segs[sg].len) { i -= a.segs[sg].len; ++sg; }
-      const gtr_segment& S = a.segs[sg];
-      float g = 0.0f;
-      for (int q = 0; q < S.nparts; ++q) g += S.src[(int64_t)q * S.pstride + i];
-      const int64_t e = S.begin + i;
-      float pv = a.tl.flat[e], mv = a.tl.flat_m[e], vv = a.tl.flat_v[e];
-      st.apply(pv, mv, vv, g);
-      a.tl.flat[e] = pv;
-      a.tl.flat_m[e] = mv;
-      a.tl.flat_v[e] = vv;
-    }
-    if (blk == 0 && a.tl.loss_part) {  // loss of the step: the readout's partials, fixed order
-      float acc = 0.0f;
-      for (int q = tid; q < a.tl.loss_nparts; q += GTR_BLOCK)
-        acc += a.tl.loss_part[(size_t)q * 2] + a.tl.loss_part[(size_t)q * 2 + 1];
-      s_acc[tid] = acc;
-      __syncthreads();
-      if (tid == 0) {
-        float t = 0.0f;
-        for (int q = 0; q < GTR_BLOCK; ++q) t += s_acc[q];
-        a.tl.loss_out[0] = t;
-        if (a.tl.loss_acc) a.tl.loss_acc[0] += (double)t;
-      }
-    } else if (blk == 0 && a.tl.loss_acc && tid == 0) {
-      a.tl.loss_acc[0] += (double)a.tl.loss_out[0];
-    }
-  }
-}
-
 // ---- small batches: the touched rows beside the weight gradients ------------------------
 // Workgroups: [weight-gradient tile chunks | touched rows].  The tiles are k_wgrad's
 // (wgrad_block: same jobs, chunks and slabs); the touched rows are k_step_tail's rows part
@@ -1285,28 +1152,6 @@ __global__ __launch_bounds__(GTR_BLOCK) void k_scatter_rows(gtr_batch bt, int mo
   if (key <= 0) return;  // padding_idx = 0
 #pragma unroll
   for (int q = 0; q < VPL; ++q) atomicAdd(dense + (size_t)key * D + d0 + q, c * s[d0 + q]);
-}
-
-// Step epilogue: advance the step / dropout-stream counters and (optionally) sum the
-// readout's pre-scaled loss partials [nparts][2] in fixed order.
-__global__ void k_step_end(int64_t* step_dev, uint32_t* rng_ctr, const float* loss_part, int nparts,
-                           float* loss_out) {
-  __shared__ float s_acc[64];
-  const int tid = threadIdx.x;
-  float acc = 0.0f;
-  if (loss_part)
-    for (int q = tid; q < nparts; q += 64) acc += loss_part[(size_t)q * 2] + loss_part[(size_t)q * 2 + 1];
-  s_acc[tid] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    if (loss_part && loss_out) {
-      float t = 0.0f;
-      for (int q = 0; q < 64; ++q) t += s_acc[q];
-      loss_out[0] = t;
-    }
-    if (step_dev) *step_dev += 1;
-    if (rng_ctr) *rng_ctr += 1;
-  }
 }
 
 
@@ -2315,89 +2160,6 @@ int gtr_wgrad_rows(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* 
   return GTR_OK;
 }
 
-int gtr_step_tail_wgrad(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* pe_tab,
-                        float* const* layer_slab, float* pe_slab, int n_chunks, int64_t slab_stride,
-                        const int64_t* layer_flat, const int64_t* pe_flat, int num_items, const gtr_tail* tail,
-                        const gtr_segment* segs, int nseg, const gtr_adam* opt, uint32_t* tile_cnt, int tile_cnt_len,
-                        gtr_stream_t stream) {
-  if (!cfg || !bt || !layers || !layer_slab || !layer_flat || !tail || !opt || !opt->step_dev || num_items <= 0 ||
-      nseg < 0 || nseg > GTR_TAILW_SEGS || (nseg > 0 && !segs) || !dim_ok(cfg->dim) || n_chunks <= 0 ||
-      !tile_cnt || 3 * cfg->num_layers + 1 > GTR_MAX_WJOBS) {
-    set_error("gtr_step_tail_wgrad: bad arguments");
-    return GTR_E_ARG;
-  }
-  const gtr_tail& t = *tail;
-  const int D = cfg->dim;
-  const int m_cap = bt->n_cap + bt->b_cap * (1 + bt->n_neg);
-  if (m_cap > GTR_BEGIN_MCAP) {
-    set_error("gtr_step_tail_wgrad: batch too large (m_cap %d > %d): use gtr_wgrad + gtr_step_tail", m_cap,
-              GTR_BEGIN_MCAP);
-    return GTR_E_ARG;
-  }
-  if (!t.lazy_consts && t.sweep_from < num_items) {
-    set_error("gtr_step_tail_wgrad: the untouched-row sweep must run in the chain (sweep_from == num_items)");
-    return GTR_E_ARG;
-  }
-  if (!t.skeys || !t.svals || !t.dx0 || !t.se || !t.coef_tgt || !t.coef_neg || !t.table || !t.table_m ||
-      !t.table_v || !t.stamp || !t.flat || !t.flat_m || !t.flat_v || (t.loss_part && (!t.loss_out || t.loss_nparts < 0))) {
-    set_error("gtr_step_tail_wgrad: missing buffers");
-    return GTR_E_ARG;
-  }
-  TailWK k{};
-  k.bt = *bt;
-  k.tl = t;
-  k.opt = *opt;
-  k.T = num_items;
-  k.D = D;
-  k.P = n_chunks;
-  k.stride = slab_stride;
-  k.cnt = tile_cnt;
-  // the same tile form k_wgrad would pick for these chunks (GTR_WGRAD=mfma|valu overrides)
-  const char* wm = getenv("GTR_WGRAD");
-  bool mfma = (bt->n_cap + n_chunks - 1) / n_chunks >= GTR_WGRAD_MFMA_ROWS;
-  if (wm && !strcmp(wm, "mfma")) mfma = true;
-  if (wm && !strcmp(wm, "valu")) mfma = false;
-  if (slab_stride % 4) mfma = false;
-  for (int l = 0; l < cfg->num_layers; ++l)
-    if (reinterpret_cast<uintptr_t>(layer_slab[l]) % 16) mfma = false;
-  int nj = 0, wblocks = 0;
-  const int rc = build_wjobs(cfg, bt, layers, t.dx0, pe_tab, layer_slab, pe_slab, layer_flat, pe_flat, n_chunks, 0,
-                             cfg->num_layers, k.jobs, nj, wblocks, mfma);
-  if (rc) return rc;
-  int tiles = 0;
-  for (int i = 0; i < nj; ++i) {
-    k.jobs[i].tile0 = tiles;
-    tiles += k.jobs[i].nt;
-    if (k.jobs[i].fW < 0 && k.jobs[i].fB < 0) { set_error("gtr_step_tail_wgrad: a job without flat offsets"); return GTR_E_ARG; }
-  }
-  if (tiles > tile_cnt_len) {
-    set_error("gtr_step_tail_wgrad: %d tile counters needed, %d given", tiles, tile_cnt_len);
-    return GTR_E_ARG;
-  }
-  k.njobs = nj;
-  k.nb_wg = wblocks;
-  k.nb_rows = (int)(((int64_t)m_cap * (D / 4) + GTR_BLOCK - 1) / GTR_BLOCK);
-  int64_t tot = 0;
-  for (int i = 0; i < nseg; ++i) {
-    k.segs[i] = segs[i];
-    tot += segs[i].len;
-  }
-  k.nseg = nseg;
-  k.small_total = (int)tot;
-  k.nb_small = (int)((tot + GTR_BLOCK - 1) / GTR_BLOCK);
-  if (k.nb_small == 0 && (t.loss_part || t.loss_acc)) k.nb_small = 1;
-  const int grid = k.nb_wg + k.nb_rows + k.nb_small;
-  hipStream_t s = (hipStream_t)stream;
-  switch (D) {
-    case 32: hipLaunchKernelGGL(k_step_tail_wgrad<32>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
-    case 64: hipLaunchKernelGGL(k_step_tail_wgrad<64>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
-    case 128: hipLaunchKernelGGL(k_step_tail_wgrad<128>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
-    default: hipLaunchKernelGGL(k_step_tail_wgrad<256>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
-  }
-  GTR_HIP_CHECK_LAUNCH();
-  return GTR_OK;
-}
-
 // the padded row slots of n_chunks chunks at capacity n_cap (SEChunks at N = n_cap)
 static int step_end_slots(int n_cap, int n_chunks) {
   const int per = (n_cap + n_chunks - 1) / n_chunks;
@@ -2611,15 +2373,6 @@ int gtr_dp_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tai
     case 128: hipLaunchKernelGGL(k_dp_tail<128>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
     default: hipLaunchKernelGGL(k_dp_tail<256>, dim3(grid), dim3(GTR_BLOCK), 0, s, k); break;
   }
-  GTR_HIP_CHECK_LAUNCH();
-  return GTR_OK;
-}
-
-int gtr_step_end(int64_t* step_dev, uint32_t* rng_ctr, const float* loss_part, int nparts, float* loss_out,
-                 gtr_stream_t stream) {
-  if (loss_part && (nparts < 0 || !loss_out)) { set_error("gtr_step_end: bad loss partials"); return GTR_E_ARG; }
-  hipLaunchKernelGGL(k_step_end, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, rng_ctr, loss_part, nparts,
-                     loss_out);
   GTR_HIP_CHECK_LAUNCH();
   return GTR_OK;
 }

@@ -1,11 +1,10 @@
 // gtr_wgrad.cuh — weight gradients of the dense parameters (lin_{query,key,value,skip}
 // weight + bias, lin_beta, the LapPE projection) as jobs of 64 x 64 output tiles summed
-// over a node-row range.  Two users:
-//   k_wgrad (gtr_bwd.hip): split-K partial slabs over P row chunks, summed by the
-//     optimizer (large batches);
-//   k_step_tail_wgrad (gtr_opt.hip): small batches, ONE chunk over all rows computed
-//     inside the step tail and applied by AdamW directly -- the same loop, so the
-//     gradients are bitwise those of k_wgrad with P = 1 + the tail's one-partial sum.
+// over a node-row range.  Users:
+//   k_wgrad (gtr_bwd.hip) and k_wgrad_rows (gtr_opt.hip): split-K partial slabs over P
+//     row chunks (wgrad_block), summed by the optimizer tail;
+//   k_step_end_small (gtr_opt.hip): takes the job list (build_wjobs, flat offsets) and
+//     runs tiles of its own that apply AdamW directly.
 #pragma once
 
 #include "gtr_common.cuh"
@@ -29,8 +28,7 @@ struct WJob {
   const float* s;   // skip rows (qkvs + 3D), row stride lda
   float* outW;      // slab destinations (k_wgrad)
   float* outB;
-  int64_t fW, fB;   // flat-buffer offsets of the same outputs (fused tail), -1: none
-  int tile0, pad_t; // first arrival counter of the job's tiles (fused tail)
+  int64_t fW, fB;   // flat-buffer offsets of the same outputs (gtr_step_end_small), -1: none
 };
 
 #define GTR_MAX_WJOBS 16
@@ -366,7 +364,7 @@ __device__ __forceinline__ void wgrad_tile_mfma(const WJob& J, int tile, int t0,
 
 // Host: the job list of layers [l_begin, l_end) (+ the LapPE projection when l_begin == 0
 // and cfg->pe_k > 0).  Slab destinations layer_slab[l] / pe_slab (k_wgrad) and/or flat
-// offsets layer_flat[l] = {w_all, b_all, w_beta} / pe_flat = {pe.w, pe.b} (fused tail);
+// offsets layer_flat[l] = {w_all, b_all, w_beta} / pe_flat = {pe.w, pe.b} (gtr_step_end_small);
 // `blocks` = workgroups for n_chunks row chunks.
 inline int build_wjobs(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* dx0,
                        const float* pe_tab, float* const* layer_slab, float* pe_slab, const int64_t* layer_flat,

@@ -190,15 +190,12 @@ _SIGS = {
     "gtr_adamw_rows": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
     "gtr_adamw_sweep": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P, P]),
     "gtr_scatter_rows": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P]),
-    "gtr_step_end": (C.c_int, [P, P, P, C.c_int, P, P]),
     "gtr_readout_grid": (C.c_int, [C.c_int]),
     "gtr_dp_pack": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P, P]),
     "gtr_dp_tail": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P]),
     "gtr_dp_union_stamp": (C.c_int, [P, i64, C.c_int, P, P, P]),
     "gtr_step_begin": (C.c_int, [P, C.c_int, P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "gtr_step_tail": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P]),
-    "gtr_step_tail_wgrad": (C.c_int, [P, P, P, P, P, P, C.c_int, C.c_int64, P, P, C.c_int, P, P, C.c_int, P, P,
-                                      C.c_int, P]),
     "gtr_wgrad_rows": (C.c_int, [P, P, P, P, P, P, P, C.c_int, i64, C.c_int, C.c_int, C.c_int, P, P, P]),
     "gtr_step_tail_small": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P]),
     "gtr_step_end_small": (C.c_int, [P, P, P, P, C.c_int, P, P, C.c_int, P, P, C.c_int, P, P]),

@@ -567,7 +567,7 @@ class Engine:
         """conv_bwd(L-1..0) + weight-gradient slabs; expects layers[L-1].dy / bn_gsum.
         With ``side``, layer l >= 1 weight gradients run on that stream concurrently
         with conv_bwd(l-1..0); the caller must join ``side`` before reading slabs.
-        ``wgrad=False``: the weight gradients are left to the fused tail.  ``rows`` =
+        ``wgrad=False``: the weight gradients are left to gtr_step_end_small.  ``rows`` =
         (tail, adam), without ``side``: the weight-gradient launch also updates the touched
         table rows (gtr_wgrad_rows)."""
         lib = L.lib()

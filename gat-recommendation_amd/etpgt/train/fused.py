@@ -8,6 +8,9 @@ launches on one stream (the blob copy, then):
   step_begin -> conv_fwd(0..L-1) -> readout_loss(FWD|LOSS|BWD) -> conv_bwd(L-1..0)
   -> wgrad(all layers) -> step_tail
 
+Single-GPU small batches end in wgrad_rows -> step_tail_small instead (the touched rows
+beside the weight gradients), or in the one launch step_end_small where it fits.
+
 step_begin advances the step / dropout counters, stamps the touched table rows and
 builds the sorted table-gradient contribution list; step_tail applies AdamW to the
 touched rows (segment sums of the contributions), to the untouched rows (g = 0: the
@@ -44,8 +47,6 @@ class FusedTrainStep:
             # the FFN variant trains data parallel (replicated or row-sharded table), with or
             # without SyncBN; SyncBN folds the gathered rows in the FFN's first GEMM (dim 64 / 128,
             # expansion 4)
-            if os.environ.get("GTR_TAILW") == "1":
-                raise NotImplementedError("the FFN variant (use_ffn=True) has no GTR_TAILW step")
             if sync_bn and not (model.embedding_dim in (64, 128) and getattr(model, "ffn_expansion", 4) == 4):
                 raise NotImplementedError("SyncBN with the FFN variant covers dim 64 / 128 at ffn_expansion 4")
         self.model = model
@@ -336,35 +337,29 @@ class FusedTrainStep:
             self.dp = DpExchange(self, self.group)
         if self.sync_bn:
             self._sync_alloc()
-        # opt-in (GTR_TAILW=1): weight gradients and optimizer tail in one launch
-        # (gtr_step_tail_wgrad: split-K tiles, each tile's last arriving chunk applies AdamW);
-        # bitwise the two launches but slower (C2 0.083 -> 0.102 ms: one workgroup per tile
-        # walks its 4k elements' partials serially); needs the sweep in the chain or a lazy table
-        # (both one-launch ends hand the tail the BatchNorm segments only -- segs_gb -- and
-        # would skip ro.w / ro.b: mean readout only)
-        mean_ro = eng.readout == "mean"
-        self.tail_wgrad = (self.dp is None and self.shard is None and m_cap <= 8192 and mean_ro
-                           and (self.lazy or t.sweep_from >= eng.T) and os.environ.get("GTR_TAILW", "0") == "1")
-        # single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
+        # The step ends in one of three ways.  The general end (large batches, data parallel,
+        # sharded) is gtr_wgrad + gtr_step_tail.
+        # Single GPU, small batches: the touched-row AdamW runs as extra workgroups of the
         # weight-gradient launch (gtr_wgrad_rows -- the rows do not depend on the weight
         # gradients) and the tail keeps the small parameters (gtr_step_tail_small); bitwise
         # the two plain launches, GTR_ROWS_EARLY=0 restores them
-        self.rows_early = (self.dp is None and self.shard is None and m_cap <= 8192 and not self.tail_wgrad
+        self.rows_early = (self.dp is None and self.shard is None and m_cap <= 8192
                            and os.environ.get("GTR_ROWS_EARLY", "1") != "0")
         # ... and where all node rows fit one staging round in LDS (n_cap <= 256 at the default
         # chunks), that pair is ONE launch whose tiles own their outputs and apply AdamW
         # themselves (gtr_step_end_small): no slabs, no tail launch; bitwise the pair,
         # GTR_STEP_END=0 restores it.  Not with FFN blocks (their slabs come from
-        # gtr_ffn_wgrad) and only with the sweep in the chain or a lazy table.  Its sums are
-        # those of the pair's VALU tiles, so it stays off where the pair would run MFMA tiles
-        # (GTR_WGRAD=mfma, or chunks of >= 128 rows under GTR_WGRAD_ROWS).
+        # gtr_ffn_wgrad) and only with the sweep in the chain or a lazy table.  It hands the
+        # tail role the BatchNorm segments only (segs_gb) and would skip ro.w / ro.b: mean
+        # readout only.  Its sums are those of the pair's VALU tiles, so it stays off where
+        # the pair would run MFMA tiles (GTR_WGRAD=mfma, or chunks of >= 128 rows under
+        # GTR_WGRAD_ROWS).
+        mean_ro = eng.readout == "mean"
         valu = os.environ.get("GTR_WGRAD") != "mfma" and -(-self.caps.n_cap // self.ws.P) < 128
         self.step_end = (self.rows_early and mean_ro and self.ws.ffns is None and (self.lazy or t.sweep_from >= eng.T) and valu
                          and bool(L.lib().gtr_step_end_small_fits(self.caps.n_cap, self.ws.P, eng.K))
                          and os.environ.get("GTR_STEP_END", "1") != "0")
-        if self.tail_wgrad or self.step_end:
-            if self.tail_wgrad:
-                self.tile_cnt = torch.zeros(4096, dtype=torch.int32, device=self.dev)
+        if self.step_end:
             lay = eng.flat.layout
             gb = [i for i in range(self.nseg)
                   if any(self.segs[i].begin == lay.seg(f"{l}.{n}").begin for l in range(eng.L) for n in ("gamma", "beta"))]
@@ -559,7 +554,7 @@ class FusedTrainStep:
         self._begin(bs, st)
         eng.run_forward(ws, cfg, bs, L.RO_FWD | L.RO_LOSS | L.RO_BWD, self.loss_kind, self.temperature, self.alpha,
                         split=self.split)
-        eng.run_backward(ws, cfg, bs, wgrad=not (self.tail_wgrad or self.step_end), split=self.split,
+        eng.run_backward(ws, cfg, bs, wgrad=not self.step_end, split=self.split,
                          rows=(self.tail, self.adam) if self.rows_early else None)
         if self.dp is not None:
             self.dp.launch_pack(bs, st)
@@ -571,16 +566,6 @@ class FusedTrainStep:
         st = torch.cuda.current_stream(self.dev).cuda_stream
         if self.dp is not None:
             self.dp.launch_tail(bs, st)
-        elif self.tail_wgrad:
-            pe = self.model.laplacian_pe._cached_pe if eng.K > 0 else None
-            ws = self.ws
-            L.check(L.lib().gtr_step_tail_wgrad(C.byref(self.cfg), C.byref(bs), ws.structs,
-                                                None if pe is None else pe.data_ptr(), ws.slab_ptrs,
-                                                None if ws.pe_slab is None else ws.pe_slab.data_ptr(), ws.P,
-                                                eng.flat.layout.slab_stride, self.layer_flat, self.pe_flat, eng.T,
-                                                C.byref(self.tail), self.segs_gb, self.nseg_gb, C.byref(self.adam),
-                                                self.tile_cnt.data_ptr(), self.tile_cnt.numel(), st),
-                    "step_tail_wgrad")
         elif self.step_end:  # weight gradients, touched rows and the small tail: one launch
             pe = self.model.laplacian_pe._cached_pe if eng.K > 0 else None
             L.check(L.lib().gtr_step_end_small(C.byref(self.cfg), C.byref(bs), self.ws.structs,

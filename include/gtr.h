@@ -25,7 +25,6 @@
  *                     torch.optim.AdamW(lr, wd) step of train_baseline.py:252-256
  *                     (trainer.py:125-127) over the item table and the dense params.
  *   gtr_scatter_rows  eager (autograd) path: dense table gradient.
- *   gtr_step_end      step / dropout-stream counters.
  *   gtr_step_begin / gtr_step_tail
  *                     one whole Trainer.train_epoch iteration (trainer.py:80-133)
  *                     is begin -> conv_fwd.. -> readout_loss -> conv_bwd.. -> wgrad
@@ -61,7 +60,7 @@
 extern "C" {
 #endif
 
-#define GTR_ABI_VERSION 9 /* 9: the folded-weight-gradient fields of gtr_config / gtr_layer / gtr_segment (added in 5) removed; 8: gtr_shard.cap_s / grad_stride / small_stride / pack_parts / node_mark (two-class exchange); 7: gtr_tail.loss_acc; 6: gtr_layer.ffn + gtr_ffn_fwd / gtr_ffn_bwd / gtr_ffn_wgrad (the FFN variant); 5: gtr_config.loss_batch, hdr[6] halo source rows (+ three fields removed in 9); 4: gtr_step_tail_wgrad on split-K slabs; 3: gtr_config.begin / ctr_add, gtr_tail.rng_inc */
+#define GTR_ABI_VERSION 9 /* (two entry points were removed under 9 without a bump -- gtr_step_tail_wgrad, added in 4, and gtr_step_end: a missing entry point fails when it is bound, no layout changed; the next bump records them) 9: the folded-weight-gradient fields of gtr_config / gtr_layer / gtr_segment (added in 5) removed; 8: gtr_shard.cap_s / grad_stride / small_stride / pack_parts / node_mark (two-class exchange); 7: gtr_tail.loss_acc; 6: gtr_layer.ffn + gtr_ffn_fwd / gtr_ffn_bwd / gtr_ffn_wgrad (the FFN variant); 5: gtr_config.loss_batch, hdr[6] halo source rows (+ three fields removed in 9); 4: gtr_step_tail_wgrad on split-K slabs; 3: gtr_config.begin / ctr_add, gtr_tail.rng_inc */
 
 #define GTR_OK 0
 #define GTR_E_ARG 1001      /* bad argument / unsupported shape */
@@ -523,23 +522,6 @@ int gtr_tail_carry_floats(int m_cap, int dim);
 int gtr_step_tail(const gtr_batch* bt, int num_items, int dim, const gtr_tail* tail,
                   const gtr_segment* segs, int nseg, const gtr_adam* opt, gtr_stream_t stream);
 
-/* Small batches (m_cap <= 8192, untouched-row sweep in the chain or a lazy table):
- * gtr_wgrad + gtr_step_tail as ONE launch (trainer.py:123-127: backward +
- * optimizer.step()).  The weight-gradient tiles write their split-K partial slabs
- * (layer_slab / pe_slab, n_chunks, slab_stride as gtr_wgrad); each tile's last arriving
- * chunk sums the n_chunks partials of its outputs in chunk order and applies AdamW;
- * touched rows and the bn_gsum segments run beside the tiles.  layer_flat [L][3] =
- * element offsets into tail->flat of each layer's w_all / b_all / w_beta; pe_flat [2] =
- * offsets of the LapPE projection weight / bias (NULL without LapPE); segs = the other
- * dense segments (BatchNorm gamma / beta from bn_gsum, <= 16); tile_cnt = tile_cnt_len
- * zeroed counters (one per tile; each launch leaves them zero).  Bitwise equal to
- * gtr_wgrad + gtr_step_tail.                                                          */
-int gtr_step_tail_wgrad(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, const float* pe_tab,
-                        float* const* layer_slab, float* pe_slab, int n_chunks, int64_t slab_stride,
-                        const int64_t* layer_flat, const int64_t* pe_flat, int num_items, const gtr_tail* tail,
-                        const gtr_segment* segs, int nseg, const gtr_adam* opt, uint32_t* tile_cnt, int tile_cnt_len,
-                        gtr_stream_t stream);
-
 /* Small batches (m_cap <= 8192; GTR_E_ARG above): gtr_wgrad and the touched-row AdamW of
  * gtr_step_tail as ONE launch of independent workgroups -- first the weight-gradient
  * tiles (arguments, slabs and results exactly gtr_wgrad's), then the touched rows
@@ -564,10 +546,12 @@ int gtr_step_tail_small(const gtr_batch* bt, int num_items, int dim, const gtr_t
  *     LapPE projection) is owned by one thread, which forms the n_chunks chunk values over
  *     the same row ranges with the same operations in the same order as gtr_wgrad's tiles,
  *     adds them in chunk order from +0 as the tail does with the slabs, and applies AdamW
- *     to the flat parameter (layer_flat / pe_flat as gtr_step_tail_wgrad);
+ *     to the flat parameter;
  *   - touched rows: as gtr_wgrad_rows;
- *   - segs (<= 16): the BatchNorm gamma / beta segments (bn_gsum), the loss sum,
- *     tail->rng_inc and tail->loss_acc as gtr_step_tail_small.
+ *   - segs (<= 16): the other dense segments (BatchNorm gamma / beta from bn_gsum), the
+ *     loss sum, tail->rng_inc and tail->loss_acc as gtr_step_tail_small.
+ * layer_flat [L][3] = element offsets into tail->flat of each layer's w_all / b_all /
+ * w_beta; pe_flat [2] = offsets of the LapPE projection weight / bias (NULL without LapPE).
  * Bit for bit gtr_wgrad_rows + gtr_step_tail_small with the same n_chunks.  Needs
  * gtr_step_end_small_fits(n_cap, n_chunks, pe_k), m_cap <= 8192, the untouched-row sweep
  * in the chain or a lazy table, 16-byte aligned activations and no FFN blocks (their
@@ -791,11 +775,6 @@ int gtr_lap_gram(const float* S, const float* Y, int n, int m, double* part, int
 /* Workgroups of gtr_readout_loss = the number of its loss / BatchNorm-sum partials
  * (gtr_tail.loss_nparts; the last layer's bn_gpart rows).                         */
 int gtr_readout_grid(int b_cap);
-
-/* step_dev += 1 (if non-NULL); rng_ctr += 1 (if non-NULL); if loss_part != NULL,
- * loss_out[0] = sum of the 2*nparts (already scaled) loss partials in order.     */
-int gtr_step_end(int64_t* step_dev, uint32_t* rng_ctr, const float* loss_part, int nparts, float* loss_out,
-                 gtr_stream_t stream);
 
 #ifdef __cplusplus
 }

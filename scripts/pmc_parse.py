@@ -39,7 +39,7 @@ def load(d, counter):
     return acc, [(k, v) for _, k, v in seq]
 
 
-STEP_END = ("k_step_tail", "k_step_tail_wgrad", "k_dp_tail", "k_shard_update")
+STEP_END = ("k_step_tail", "k_step_end_small", "k_dp_tail", "k_shard_update")
 
 
 def per_step(seq):

@@ -69,13 +69,8 @@ def test_ffn_models_refuse_unsupported_fused_steps_and_shapes(monkeypatch):
     from etpgt.train.fused import FusedTrainStep
 
     # data parallel on the replicated or row-sharded table, with or without SyncBN, is
-    # supported (tests/test_gpu_ffn_dp.py); GTR_TAILW and SyncBN outside dim 64 / 128 at
-    # expansion 4 refuse up front
-    m = create_graph_transformer(50, embedding_dim=64, hidden_dim=64, num_layers=2, num_heads=2, use_ffn=True)
-    monkeypatch.setenv("GTR_TAILW", "1")
-    with pytest.raises(NotImplementedError, match="use_ffn"):
-        FusedTrainStep(m)
-    monkeypatch.delenv("GTR_TAILW")
+    # supported (tests/test_gpu_ffn_dp.py); SyncBN outside dim 64 / 128 at expansion 4
+    # refuses up front
     m2 = create_graph_transformer(50, embedding_dim=64, hidden_dim=64, num_layers=2, num_heads=2, use_ffn=True,
                                   ffn_expansion=2)
     with pytest.raises(NotImplementedError, match="ffn_expansion 4"):

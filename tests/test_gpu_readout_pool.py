@@ -258,7 +258,7 @@ def _fused_vs_trio(kind, D, H, K, loss, B, n, temperature=1.0, steps=5, **kw):
         if kind == "attention":  # d loss / d bias == 0 exactly: all noise, bounded by 2 lr per step
             trio.noise[BIAS][:] = True
     np.testing.assert_allclose(losses, rlosses, rtol=1e-3)
-    assert fused.step_end is False and fused.tail_wgrad is False
+    assert fused.step_end is False
     fused.flush()
     # every trained parameter elementwise, the whole item table included (a missing sweep
     # slot would leave its untouched rows a step behind)

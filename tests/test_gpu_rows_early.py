@@ -75,12 +75,19 @@ def _run_equal(monkeypatch, bl, D, H, K, loss, opt="adamw", lazy=False, caps=Non
 
 
 @pytest.mark.parametrize("lazy", [False, True])
-@pytest.mark.parametrize("D,H,K,loss,opt", [(64, 1, 0, "bpr", "adamw"), (128, 4, 16, "listwise", "adamw"),
-                                            (32, 2, 8, "dual", "adamw"), (64, 2, 0, "bpr", "adam")])
-def test_rows_early_bitwise_equals_separate_launches(D, H, K, loss, opt, lazy, monkeypatch):
+@pytest.mark.parametrize("D,H,K,loss,opt,wgrad", [
+    pytest.param(64, 1, 0, "bpr", "adamw", None, id="64-1-0-bpr-adamw"),
+    pytest.param(128, 4, 16, "listwise", "adamw", None, id="128-4-16-listwise-adamw"),
+    pytest.param(128, 4, 16, "listwise", "adamw", "mfma", id="128-4-16-listwise-adamw-mfma"),
+    pytest.param(32, 2, 8, "dual", "adamw", None, id="32-2-8-dual-adamw"),
+    pytest.param(64, 2, 0, "bpr", "adam", None, id="64-2-0-bpr-adam")])
+def test_rows_early_bitwise_equals_separate_launches(D, H, K, loss, opt, wgrad, lazy, monkeypatch):
     """Four steps on different batches (B = 32, dropout 0.1): every step's loss, every
     parameter and buffer and the AdamW moments of the table and of the flat parameters,
-    with the eager table and with the lazy one."""
+    with the eager table and with the lazy one; GTR_WGRAD=mfma forces the MFMA tiles onto
+    both sides' 32-row chunks (where the one-launch end stays off)."""
+    if wgrad:
+        monkeypatch.setenv("GTR_WGRAD", wgrad)
     n = 100 if loss == "listwise" else 5
     _run_equal(monkeypatch, batches(data(), 32, n, 4, seed=17), D, H, K, loss, opt, lazy)
 
