@@ -82,18 +82,11 @@ struct BBK {
   int64_t stride;               // cursor advance per batch (B; the global batch across ranks)
 };
 
-// The session's last max_len clicks (one per lane, lanes >= len hold INT_MAX), its
-// target, and the sorted unique context (lane r < u holds the r-th id).  Whole wave.
-__device__ __forceinline__ int session_nodes(const int32_t* sess_ptr, const int32_t* sess_items, int max_len,
-                                             int s, int lane, int* s_uq, int& uq, int& len, int& tgt, int& click) {
-  const int c0 = sess_ptr[s], c1 = sess_ptr[s + 1];
-  len = min(c1 - c0, max_len);
-  const int base = c1 - len;
-  click = lane < len ? sess_items[base + lane] : 0x7FFFFFFF;
-  tgt = __shfl(click, len > 0 ? len - 1 : 0);
-  int v = lane < len - 1 ? click : 0x7FFFFFFF;  // context = all but the last
+// Bitonic sort of one value per lane across the wave (INT_MAX = no value), then the
+// unique values in ascending order: lane r < u holds the r-th in uq and s_uq[r].  Whole wave.
+__device__ __forceinline__ int wave_sort_unique(int v, int lane, int* s_uq, int& uq) {
 #pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {           // bitonic sort across the wave
+  for (int k = 2; k <= 64; k <<= 1) {
 #pragma unroll
     for (int j = k >> 1; j > 0; j >>= 1) {
       const int o = __shfl_xor(v, j);
@@ -113,6 +106,19 @@ __device__ __forceinline__ int session_nodes(const int32_t* sess_ptr, const int3
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   uq = lane < u ? s_uq[lane] : 0;
   return u;
+}
+
+// The session's last max_len clicks (one per lane, lanes >= len hold INT_MAX), its
+// target, and the sorted unique context (lane r < u holds the r-th id).  Whole wave.
+__device__ __forceinline__ int session_nodes(const int32_t* sess_ptr, const int32_t* sess_items, int max_len,
+                                             int s, int lane, int* s_uq, int& uq, int& len, int& tgt, int& click) {
+  const int c0 = sess_ptr[s], c1 = sess_ptr[s + 1];
+  len = min(c1 - c0, max_len);
+  const int base = c1 - len;
+  click = lane < len ? sess_items[base + lane] : 0x7FFFFFFF;
+  tgt = __shfl(click, len > 0 ? len - 1 : 0);
+  const int v = lane < len - 1 ? click : 0x7FFFFFFF;  // context = all but the last
+  return wave_sort_unique(v, lane, s_uq, uq);
 }
 
 // Induced adjacency of the u unique ids in s_uq: row[x] bit y / col[y] bit x for every
@@ -226,20 +232,14 @@ struct BBWave {
   int inoff[64];
 };
 
-// One wave writes session b (epoch position pos, first edge e0, first node n0): nodes,
-// induced edges, CSR by destination and by source, target, negatives.
-__device__ void write_session(const BBK& a, int b, int64_t pos, int e0, int n0, BBWave& L) {
-  const int lane = threadIdx.x & 63;
-  const int s = a.order[pos % a.S];
-  int uq, len, tgt, click;
-  const int u = session_nodes(a.sess_ptr, a.sess_items, a.max_len, s, lane, L.uq, uq, len, tgt, click);
-  session_adjacency(a.slots, a.mask, a.T, u, lane, L.uq, L.row, L.col);
-  unsigned long long* s_row_w = L.row;
+// CSR write-out of one session from its row / col bitmasks (row[x] bit y and col[y] bit x:
+// edge x -> y; any directed mask): node ids, in-edges by destination with sources
+// ascending, out-edges by source with destinations ascending and their positions in the
+// destination order.  First node n0, first edge e0.  Whole wave.
+__device__ __forceinline__ void session_csr(const gtr_batch& bt, int u, int uq, int e0, int n0, int lane, BBWave& L) {
   unsigned long long* s_col_w = L.col;
   int* s_inoff_w = L.inoff;
-  int* s_clk_w = L.clk;
-  const gtr_batch& bt = a.bt;
-  const unsigned long long row = lane < u ? s_row_w[lane] : 0ull;
+  const unsigned long long row = lane < u ? L.row[lane] : 0ull;
   const unsigned long long col = lane < u ? s_col_w[lane] : 0ull;
   const int indeg = __popcll(col), outdeg = __popcll(row);
   int iin = indeg, iout = outdeg;
@@ -250,7 +250,6 @@ __device__ void write_session(const BBK& a, int b, int64_t pos, int e0, int n0, 
   }
   const int in_off = iin - indeg, out_off = iout - outdeg;
   s_inoff_w[lane] = in_off;
-  s_clk_w[lane] = click;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -275,6 +274,20 @@ __device__ void write_session(const BBK& a, int b, int64_t pos, int e0, int n0, 
       od[k] = n0 + y;
     }
   }
+}
+
+// One wave writes session b (epoch position pos, first edge e0, first node n0): nodes,
+// induced edges, CSR by destination and by source, target, negatives.
+__device__ void write_session(const BBK& a, int b, int64_t pos, int e0, int n0, BBWave& L) {
+  const int lane = threadIdx.x & 63;
+  const int s = a.order[pos % a.S];
+  int uq, len, tgt, click;
+  const int u = session_nodes(a.sess_ptr, a.sess_items, a.max_len, s, lane, L.uq, uq, len, tgt, click);
+  session_adjacency(a.slots, a.mask, a.T, u, lane, L.uq, L.row, L.col);
+  int* s_clk_w = L.clk;
+  const gtr_batch& bt = a.bt;
+  s_clk_w[lane] = click;  // read after session_csr's wave barrier
+  session_csr(bt, u, uq, e0, n0, lane, L);
   if (lane == 0) const_cast<int32_t*>(bt.target)[b] = tgt;
   // negatives: uniform in [1, T) rejecting the session's clicks, 64 candidates a round,
   // rejected for as long as it takes (dataloader.py:107-124 loops until it has n).  Only a
@@ -427,6 +440,167 @@ __global__ __launch_bounds__(BB_BLOCK) void k_bb_one(BBK a) {
   write_session(a, b, cur + b, s_ep[b], s_np[b], s_w[w]);
 }
 
+// ---- serving: ad-hoc request lists -> batch image (etpgt/serving/recommender.py:99-117) ----
+// A request's graph differs from a training example's: every item is a node (no target
+// split), and an edge is any stored row (item_i, item_j), item_i != item_j, in the
+// orientation the file holds -- so the hash holds ordered pairs and both (x, y) and (y, x)
+// are probed.  Launches: k_sv_count (wave per request: node / edge / exclusion counts and
+// the batch totals the host sizes the image from), then k_sv_scan (one workgroup: offsets,
+// header, tails, excl_ptr) and k_sv_write (wave per request).
+
+#define SV_STATUS_COUNTS 4  // the counts handed to the build are not this request buffer's
+
+struct SVK {
+  BBK k;                      // bt, slots, mask, scratch, status, start, B, T, R (what the shared parts read)
+  const int32_t* req_ptr;     // [B+1] item offsets
+  const int32_t* req_items;   // items, request order
+  const int32_t* counts;      // [3 * B]: nodes, edges, excluded ids of each request
+  int32_t* excl_ptr;          // [B+1]
+  int32_t* excl_ids;          // [x_cap]
+  int64_t x_cap;
+};
+
+// The request's items (at most 64; one per lane) sorted and made unique.  Whole wave.
+__device__ __forceinline__ int request_nodes(const int32_t* req_ptr, const int32_t* req_items, int b, int lane,
+                                             int* s_uq, int& uq) {
+  const int c0 = req_ptr[b];
+  const int len = max(0, min(req_ptr[b + 1] - c0, 64));
+  const int v = lane < len ? req_items[c0 + lane] : 0x7FFFFFFF;
+  return wave_sort_unique(v, lane, s_uq, uq);
+}
+
+// Induced adjacency of the u unique ids in s_uq over ORDERED pairs: row[x] bit y / col[y]
+// bit x for every stored (s_uq[x], s_uq[y]), x != y.  Whole wave; returns the edge count.
+__device__ __forceinline__ int request_adjacency(const uint64_t* slots, uint64_t mask, int T, int u, int lane,
+                                                 const int* s_uq, unsigned long long* s_row,
+                                                 unsigned long long* s_col) {
+  s_row[lane] = 0ull;
+  s_col[lane] = 0ull;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int q = lane; q < u * u; q += 64) {
+    const int x = q / u, y = q - x * u;
+    if (x == y) continue;
+    const uint64_t key = (uint64_t)s_uq[x] * (uint64_t)T + (uint64_t)s_uq[y];
+    if (edge_member(slots, mask, key)) {
+      atomicOr(&s_row[x], 1ull << y);
+      atomicOr(&s_col[y], 1ull << x);
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  int e = lane < u ? __popcll(s_row[lane]) : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+  return e;
+}
+
+// counts[3b..] = nodes, edges, excluded ids ({0} U nodes) of request b; totals += (N, E).
+__global__ __launch_bounds__(BB_BLOCK) void k_sv_count(const int32_t* req_ptr, const int32_t* req_items, int B,
+                                                       const uint64_t* slots, uint64_t mask, int T,
+                                                       int32_t* counts, int32_t* totals) {
+  __shared__ int s_uq[BB_WAVES][64];
+  __shared__ unsigned long long s_row[BB_WAVES][64];
+  __shared__ unsigned long long s_col[BB_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int b = blockIdx.x * BB_WAVES + w;
+  if (b >= B) return;
+  int uq;
+  const int u = request_nodes(req_ptr, req_items, b, lane, s_uq[w], uq);
+  const int e = request_adjacency(slots, mask, T, u, lane, s_uq[w], s_row[w], s_col[w]);
+  if (lane == 0) {
+    counts[3 * b] = u;
+    counts[3 * b + 1] = e;
+    counts[3 * b + 2] = u + ((u > 0 && s_uq[w][0] == 0) ? 0 : 1);
+    atomicAdd(totals, u);
+    atomicAdd(totals + 1, e);
+  }
+}
+
+// Single workgroup, as k_bb_scan: offsets of the batch from the per-request counts
+// (scratch[3b..] = edge, node offset), excl_ptr, header, tails.
+__global__ __launch_bounds__(BB_SCAN_BLOCK) void k_sv_scan(SVK a) {
+  __shared__ int s_np[BB_BMAX + 1];
+  __shared__ int s_wsum[3][BB_SCAN_BLOCK / 64];
+  __shared__ int s_tot[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int B = a.k.B;
+  const int per = (B + BB_SCAN_BLOCK - 1) / BB_SCAN_BLOCK;
+  const int b0 = min(B, tid * per), b1 = min(B, b0 + per);
+  int sn = 0, se = 0, sx = 0;
+  for (int b = b0; b < b1; ++b) {
+    sn += a.counts[3 * b];
+    se += a.counts[3 * b + 1];
+    sx += a.counts[3 * b + 2];
+  }
+  int in = sn, ie = se, ix = sx;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int tn = __shfl_up(in, o), te = __shfl_up(ie, o), tx = __shfl_up(ix, o);
+    if (lane >= o) { in += tn; ie += te; ix += tx; }
+  }
+  if (lane == 63) { s_wsum[0][wave] = in; s_wsum[1][wave] = ie; s_wsum[2][wave] = ix; }
+  __syncthreads();
+  if (tid == 0) {
+    int acc[3] = {0, 0, 0};
+    for (int w = 0; w < BB_SCAN_BLOCK / 64; ++w) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int x = s_wsum[c][w];
+        s_wsum[c][w] = acc[c];
+        acc[c] += x;
+      }
+    }
+    s_tot[0] = acc[0]; s_tot[1] = acc[1]; s_tot[2] = acc[2];
+  }
+  __syncthreads();
+  int on = s_wsum[0][wave] + in - sn, oe = s_wsum[1][wave] + ie - se, ox = s_wsum[2][wave] + ix - sx;
+  int32_t* off = a.k.scratch;
+  for (int b = b0; b < b1; ++b) {
+    s_np[b] = on;
+    off[3 * b] = oe;
+    off[3 * b + 1] = on;
+    a.excl_ptr[b] = ox;
+    on += a.counts[3 * b];
+    oe += a.counts[3 * b + 1];
+    ox += a.counts[3 * b + 2];
+  }
+  const int N = s_tot[0], E = s_tot[1], X = s_tot[2];
+  if (tid == 0) { s_np[B] = N; a.excl_ptr[B] = X; }
+  __syncthreads();
+  const gtr_batch& bt = a.k.bt;
+  const bool over = N > bt.n_cap || E > bt.e_cap || B > bt.b_cap || (int64_t)X > a.x_cap;
+  write_header_tails<BB_SCAN_BLOCK>(a.k, s_np, off, 3, N, E, over, 0);
+}
+
+// Wave per request, offsets from k_sv_scan: nodes, induced edges, both CSRs, a zero
+// target, the exclusion list.  A request whose counts differ from the ones the offsets were
+// scanned from writes nothing and flags SV_STATUS_COUNTS.
+__global__ __launch_bounds__(BB_BLOCK) void k_sv_write(SVK a) {
+  __shared__ BBWave s_w[BB_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int b = blockIdx.x * BB_WAVES + w;
+  if (a.k.status[0] != 0 || b >= a.k.B) return;
+  BBWave& L = s_w[w];
+  int uq;
+  const int u = request_nodes(a.req_ptr, a.req_items, b, lane, L.uq, uq);
+  const int e = request_adjacency(a.k.slots, a.k.mask, a.k.T, u, lane, L.uq, L.row, L.col);
+  const int zero = (u > 0 && L.uq[0] == 0) ? 0 : 1;  // 1: id 0 goes in front of the nodes
+  if (u != a.counts[3 * b] || e != a.counts[3 * b + 1] || u + zero != a.counts[3 * b + 2]) {
+    if (lane == 0) __hip_atomic_fetch_or(a.k.status + 1, SV_STATUS_COUNTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  session_csr(a.k.bt, u, uq, a.k.scratch[3 * b], a.k.scratch[3 * b + 1], lane, L);
+  int32_t* ex = a.excl_ids + a.excl_ptr[b];
+  if (lane == 0) {
+    const_cast<int32_t*>(a.k.bt.target)[b] = 0;
+    if (zero) ex[0] = 0;
+  }
+  if (lane < u) ex[zero + lane] = uq;
+}
+
 }  // namespace
 
 extern "C" int gtr_edge_hash_slots(int64_t num_edges, int64_t* slots) {
@@ -511,4 +685,50 @@ extern "C" int gtr_build_batch(const gtr_sessions* ss, const uint64_t* slots, in
                                gtr_stream_t stream) {
   return gtr_build_batch_strided(ss, slots, num_slots, max_len, order, cursor, B, (int64_t)B, row_group, seed, out,
                                  scratch, start, status, stream);
+}
+
+extern "C" int gtr_serve_counts(const gtr_requests* rq, const uint64_t* slots, int64_t num_slots, int32_t* counts,
+                                int32_t* totals, gtr_stream_t stream) {
+  if (!rq || !rq->req_ptr || !rq->req_items || !slots || !counts || !totals || rq->num_requests <= 0 ||
+      rq->num_requests > BB_BMAX || rq->num_items < 1 || num_slots < 1024 || (num_slots & (num_slots - 1)) != 0) {
+    set_error("gtr_serve_counts: bad arguments (1 <= requests <= %d, slots a power of two)", BB_BMAX);
+    return GTR_E_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(int32_t), s);
+  if (e != hipSuccess) { set_error("gtr_serve_counts: %s", hipGetErrorString(e)); return (int)e; }
+  hipLaunchKernelGGL(k_sv_count, dim3((rq->num_requests + BB_WAVES - 1) / BB_WAVES), dim3(BB_BLOCK), 0, s,
+                     rq->req_ptr, rq->req_items, rq->num_requests, slots, (uint64_t)(num_slots - 1), rq->num_items,
+                     counts, totals);
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}
+
+extern "C" int gtr_serve_build(const gtr_requests* rq, const uint64_t* slots, int64_t num_slots,
+                               const int32_t* counts, int row_group, const gtr_batch* out, int32_t* excl_ptr,
+                               int32_t* excl_ids, int64_t excl_cap, int32_t* scratch, int32_t* status,
+                               gtr_stream_t stream) {
+  if (!rq || !rq->req_ptr || !rq->req_items || !slots || !counts || !out || !excl_ptr || !excl_ids || !scratch ||
+      !status || rq->num_requests <= 0 || rq->num_requests > BB_BMAX || rq->num_requests > out->b_cap ||
+      rq->num_items < 1 || row_group <= 0 || out->n_neg != 0 || excl_cap < 1 || num_slots < 1024 ||
+      (num_slots & (num_slots - 1)) != 0 || ((uintptr_t)scratch & 7) != 0) {
+    set_error("gtr_serve_build: bad arguments (1 <= requests <= min(b_cap, %d), n_neg = 0, scratch 8-byte aligned)",
+              BB_BMAX);
+    return GTR_E_ARG;
+  }
+  SVK a{};
+  a.k.bt = *out;
+  a.k.slots = slots; a.k.mask = (uint64_t)(num_slots - 1);
+  a.k.start = reinterpret_cast<int64_t*>(scratch);  // the shared header writer records a batch start (0 here)
+  a.k.scratch = scratch + 2;
+  a.k.status = status;
+  a.k.B = rq->num_requests; a.k.T = rq->num_items; a.k.R = row_group;
+  a.req_ptr = rq->req_ptr; a.req_items = rq->req_items; a.counts = counts;
+  a.excl_ptr = excl_ptr; a.excl_ids = excl_ids; a.x_cap = excl_cap;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_sv_scan, dim3(1), dim3(BB_SCAN_BLOCK), 0, s, a);
+  GTR_HIP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_sv_write, dim3((a.k.B + BB_WAVES - 1) / BB_WAVES), dim3(BB_BLOCK), 0, s, a);
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
 }

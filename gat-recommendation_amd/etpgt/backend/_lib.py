@@ -136,6 +136,10 @@ class GtrSessions(C.Structure):
     ]
 
 
+class GtrRequests(C.Structure):
+    _fields_ = [("req_ptr", P), ("req_items", P), ("num_requests", i32), ("num_items", i32)]
+
+
 class GtrSweep(C.Structure):
     _fields_ = [
         ("table", P), ("m", P), ("v", P), ("stamp", P), ("opt", GtrAdam), ("bounds", i64 * (SWEEP_SLOTS + 1)),
@@ -208,6 +212,8 @@ _SIGS = {
     "gtr_session_counts": (C.c_int, [P, P, i64, C.c_int, P, P, P]),
     "gtr_build_batch": (C.c_int, [P, P, i64, C.c_int, P, P, C.c_int, C.c_int, u32, P, P, P, P, P]),
     "gtr_build_batch_strided": (C.c_int, [P, P, i64, C.c_int, P, P, C.c_int, i64, C.c_int, u32, P, P, P, P, P]),
+    "gtr_serve_counts": (C.c_int, [P, P, i64, P, P, P]),
+    "gtr_serve_build": (C.c_int, [P, P, i64, P, C.c_int, P, P, P, i64, P, P, P]),
     "gtr_lap_build": (C.c_int, [P, P, C.c_int, P, P, P]),
     "gtr_lap_plan": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P]),
     "gtr_lap_spmm": (C.c_int, [P, P, C.c_int, C.c_int, P, i64, P, i64, P, P, P, f32, f32, P]),

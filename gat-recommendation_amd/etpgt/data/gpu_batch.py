@@ -16,11 +16,17 @@ uniform in [1, T) rejecting the session's clicks.  The reference draws negatives
 ``torch.randint`` on the host; here they come from a counter-based hash of (seed, batch
 position, draw) — the same distribution, reproducible on the device
 (oracle/batch_ref.py restates the stream for the parity tests).
+
+Serving builds the same image from ad-hoc request lists that live in no store
+(``GpuServingGraph`` + ``GpuRequestBuilder``, ``gtr_serve_counts`` / ``gtr_serve_build``),
+under serving's graph rules: every item of a request is a node, edges keep the stored
+orientation, self-loops are dropped (etpgt/serving/recommender.py:88-117).
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 
 import numpy as np
 import torch
@@ -224,6 +230,157 @@ class GpuBatchBuilder:
         N, _ = self._sizes_at(self.pos, B)
         caps, blob = self.build(None, B)
         return DeviceBatch(caps, blob, N, B, self.n_neg)
+
+
+MAX_REQUEST_ITEMS = 64   # one item per lane of the wave that builds a request's graph
+MAX_REQUESTS = 16384     # requests per build (BB_BMAX of csrc/gtr_batchgen.hip)
+
+
+def pack_requests(requests, num_items: int) -> tuple[np.ndarray, np.ndarray]:
+    """Host-side validation of a batch of serving requests (lists of item ids) and their
+    ragged upload form: (req_ptr [B+1] int32, req_items int32, request order).  Runs before
+    anything is uploaded, so an id outside the table never reaches a kernel: an empty
+    request raises ``ValueError("session_items must not be empty.")``, one of more than
+    ``MAX_REQUEST_ITEMS`` items ``ValueError``, an id outside ``[0, num_items)``
+    ``IndexError`` (what the single-request route raises for it)."""
+    lens = np.fromiter(map(len, requests), np.int64, len(requests))
+    if lens.size and lens.min() == 0:
+        raise ValueError("session_items must not be empty.")
+    if lens.size and lens.max() > MAX_REQUEST_ITEMS:
+        raise ValueError(f"a request of {int(lens.max())} items is over the device builder's limit of "
+                         f"{MAX_REQUEST_ITEMS} items per session")
+    items = np.array(list(itertools.chain.from_iterable(requests)), dtype=np.int64).reshape(-1)
+    if items.size and (items.min() < 0 or items.max() >= num_items):
+        raise IndexError(f"x holds item ids outside [0, {num_items})")
+    ptr = np.zeros(lens.size + 1, np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    return ptr.astype(np.int32), items.astype(np.int32)
+
+
+class GpuServingGraph:
+    """The co-occurrence graph as serving reads it (etpgt/serving/recommender.py:88-97),
+    resident in HBM: an open-addressing hash of the ORDERED pairs ``item_i * T + item_j`` of
+    every stored row with ``item_i != item_j`` -- whatever orientation the file holds, both
+    included, self-loops dropped.  (Training's hash assumes ``item_i <= item_j``.)  Rows with
+    an end outside ``[0, T)`` can never lie inside a validated session and are left out."""
+
+    def __init__(self, item_i, item_j, num_items: int, device):
+        i = np.asarray(item_i, np.int64).reshape(-1)
+        j = np.asarray(item_j, np.int64).reshape(-1)
+        if i.shape != j.shape:
+            raise ValueError("item_i and item_j must have the same length")
+        self.device = torch.device(device)
+        self.T = int(num_items)
+        keep = (i != j) & (i >= 0) & (j >= 0) & (i < self.T) & (j < self.T)
+        keys = np.unique(i[keep] * self.T + j[keep])
+        self.num_edges = int(keys.size)
+        lib = L.lib()
+        ns = C.c_int64(0)
+        L.check(lib.gtr_edge_hash_slots(int(keys.size), C.byref(ns)), "edge_hash_slots")
+        self.num_slots = int(ns.value)
+        self.slots = torch.empty(self.num_slots, dtype=torch.int64, device=self.device)
+        keys_d = torch.from_numpy(keys).to(self.device)
+        L.check(lib.gtr_edge_hash_build(keys_d.data_ptr(), int(keys.size), self.slots.data_ptr(), self.num_slots,
+                                        torch.cuda.current_stream(self.device).cuda_stream), "edge_hash_build")
+        torch.cuda.current_stream(self.device).synchronize()  # keys_d is freed on return
+
+
+class ServingBatch:
+    """One built batch of requests: ``batch`` (a ``DeviceBatch`` the model takes),
+    ``excl_ptr`` [B+1] / ``excl_ids`` (device int32: request b may not be recommended the
+    ascending ids ``excl_ids[excl_ptr[b]:excl_ptr[b+1]]`` = {0} and its own items -- the
+    arguments of ``torch.ops.etpgt.score_topk``) and the batch's node / edge counts."""
+
+    def __init__(self, batch, excl_ptr, excl_ids, num_nodes: int, num_edges: int):
+        self.batch, self.excl_ptr, self.excl_ids = batch, excl_ptr, excl_ids
+        self.num_nodes, self.num_edges = int(num_nodes), int(num_edges)
+
+
+class GpuRequestBuilder:
+    """Session subgraphs of a batch of ad-hoc requests, built on the device
+    (``gtr_serve_counts`` + ``gtr_serve_build``): per request the sorted unique ids of all
+    its items as nodes and the stored edges among them, batched into the packed image of
+    ``blob_layout`` (no negatives, targets zero), plus the masked top-k's exclusion lists.
+
+    Host work per batch: the validation and two uploads of ``pack_requests`` (one H2D copy
+    each for ``req_ptr`` and ``req_items``), and ONE 8-byte device-to-host copy -- the edge
+    count is not known before the hash probes, so the count pass's totals (N, E) come back
+    to pick ``Caps.bucket(N, B, max(E, 1), 0)``.  Images, exclusion buffers and scratch are
+    cached per bucket and REUSED: a ``ServingBatch`` is valid until the next ``build``."""
+
+    def __init__(self, graph: GpuServingGraph):
+        self.graph = graph
+        dev = graph.device
+        self.status = torch.zeros(2, dtype=torch.int32, device=dev)  # as GpuBatchBuilder.status
+        self.totals = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.counts = None  # [3 * requests]: nodes, edges, excluded ids
+        self._bufs: dict[Caps, tuple] = {}
+
+    def build(self, requests, caps: Caps | None = None, blob: torch.Tensor | None = None,
+              check: bool = True) -> ServingBatch:
+        """Build ``requests`` (1..16384 lists of 1..64 item ids in [0, T)).  ``caps`` /
+        ``blob``: build at these capacities / into this image instead of the cached one
+        of the batch's own bucket (tests and tools); ``check=False`` leaves the status word
+        to a later ``check_status()``."""
+        ptr, items = pack_requests(requests, self.graph.T)
+        return self.build_packed(ptr, items, caps, blob, check)
+
+    def build_packed(self, ptr: np.ndarray, items: np.ndarray, caps: Caps | None = None,
+                     blob: torch.Tensor | None = None, check: bool = True) -> ServingBatch:
+        """``build`` from the validated upload form of ``pack_requests``."""
+        from etpgt.backend.engine import Engine
+
+        g = self.graph
+        dev = g.device
+        B = int(ptr.size) - 1
+        if not 0 < B <= MAX_REQUESTS:
+            raise ValueError(f"a build takes 1..{MAX_REQUESTS} requests (got {B})")
+        ptr_d = torch.from_numpy(ptr).to(dev)
+        items_d = torch.from_numpy(items).to(dev)
+        if self.counts is None or self.counts.numel() < 3 * B:
+            self.counts = torch.zeros(3 * B, dtype=torch.int32, device=dev)
+        rq = L.GtrRequests()
+        rq.req_ptr, rq.req_items, rq.num_requests, rq.num_items = ptr_d.data_ptr(), items_d.data_ptr(), B, g.T
+        lib = L.lib()
+        st = torch.cuda.current_stream(dev).cuda_stream
+        L.check(lib.gtr_serve_counts(C.byref(rq), g.slots.data_ptr(), g.num_slots, self.counts.data_ptr(),
+                                     self.totals.data_ptr(), st), "serve_counts")
+        N, E = (int(v) for v in self.totals.tolist())  # the batch's one device-to-host copy
+        if caps is None:
+            caps = Caps.bucket(N, B, max(E, 1), 0)
+        if caps.n_neg != 0 or B > caps.b_cap:
+            raise ValueError(f"{B} requests need capacities with b_cap >= {B} and no negatives (got {caps})")
+        total = blob_layout(caps)["_total"]
+        bufs = self._bufs.get(caps)
+        if bufs is None:
+            bufs = (torch.zeros(total, dtype=torch.int32, device=dev),
+                    torch.zeros(caps.b_cap + 1, dtype=torch.int32, device=dev),
+                    torch.zeros(caps.n_cap + caps.b_cap, dtype=torch.int32, device=dev),
+                    torch.zeros(3 * caps.b_cap + 2, dtype=torch.int32, device=dev))
+            while len(self._bufs) >= 8:
+                self._bufs.pop(next(iter(self._bufs)))
+            self._bufs[caps] = bufs
+        own, excl_ptr, excl_ids, scratch = bufs
+        if blob is None:
+            blob = own
+        elif blob.numel() != total or blob.dtype != torch.int32 or blob.device != own.device:
+            raise ValueError(f"blob must be {total} int32 words on {own.device}")
+        bs = Engine.batch_struct(caps, blob)
+        L.check(lib.gtr_serve_build(C.byref(rq), g.slots.data_ptr(), g.num_slots, self.counts.data_ptr(), caps.R,
+                                    C.byref(bs), excl_ptr.data_ptr(), excl_ids.data_ptr(), excl_ids.numel(),
+                                    scratch.data_ptr(), self.status.data_ptr(), st), "serve_build")
+        if check:
+            self.check_status()
+        return ServingBatch(DeviceBatch(caps, blob, N, B, 0), excl_ptr[: B + 1], excl_ids, N, E)
+
+    def check_status(self) -> None:
+        """Raise if a build since the last check failed (host sync)."""
+        code = int(self.status[1].item())
+        self.status.zero_()
+        if code & 4:
+            raise RuntimeError("GPU request build: the per-request counts do not belong to these requests")
+        if code & 1:
+            raise RuntimeError("GPU batch exceeded its capacities")
 
 
 class DeviceBatch:

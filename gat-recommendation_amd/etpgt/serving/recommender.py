@@ -11,6 +11,13 @@ MI355X path: the forward is the HIP layer stack (eval mode) and the masked full-
 scoring + top-k is ``gtr_score_topk_masked`` (MFMA scores in registers, the exclusion
 applied before selection) — no [T] score vector is materialised.  Checkpoints load with
 ``torch.load(weights_only=True)``.
+
+``recommend`` serves one request: its graph is built in Python and every kernel runs at
+B = 1.  ``recommend_batch`` serves a list of requests with the same contract per request
+and no per-request host work: the session graphs and the exclusion lists are built on the
+device (``etpgt.data.gpu_batch.GpuRequestBuilder``, ``gtr_serve_build``), then ONE eval
+forward and ONE masked top-k run for the whole batch (a backlog, offline candidate
+generation, an endpoint that micro-batches).
 """
 
 from __future__ import annotations
@@ -25,6 +32,7 @@ import torch
 
 from etpgt.backend.ops import score_topk
 from etpgt.data.batch import SessionBatch
+from etpgt.data.gpu_batch import MAX_REQUESTS, GpuRequestBuilder, GpuServingGraph, pack_requests
 from etpgt.model import create_graph_transformer_optimized
 
 
@@ -81,6 +89,10 @@ class Recommender:
             if i != j:  # no self-loops for serving message passing (recommender.py:95)
                 adjacency[int(i)].add(int(j))
         self._adjacency = adjacency
+        # the same graph on the device for recommend_batch (ordered pairs, no self-loops)
+        self._device_graph = GpuServingGraph(edges["item_i"].to_numpy(), edges["item_j"].to_numpy(),
+                                             self.num_items, self.device)
+        self._request_builder = GpuRequestBuilder(self._device_graph)
 
     def _build_session_graph(self, items: list[int]) -> SessionBatch:
         seen = set(int(v) for v in items)
@@ -118,6 +130,65 @@ class Recommender:
             ids += excl[: k - live]
             scores += [float("-inf")] * (k - live)
         return ids, scores
+
+    def validate_batch(self, requests):
+        """The host-side checks of ``recommend_batch`` (no device work): what ``recommend``
+        raises for each request, before anything is uploaded.  Returns the requests' upload
+        form (``pack_requests``) and their ``k``."""
+        ptr, items = pack_requests([r.session_items for r in requests], self.num_items)
+        ks = [int(r.k) for r in requests]
+        if ks and max(ks) > self.num_items:
+            raise RuntimeError("selected index k out of range")
+        return ptr, items, ks
+
+    @torch.no_grad()
+    def recommend_batch(self, requests) -> list[tuple[list[int], list[float]]]:
+        """``recommend`` for a list of requests: one (item_ids, scores) per request, in
+        request order, each with ``recommend``'s contract (top-k best first, the request's
+        own items and row 0 never returned; a ``k`` past the unmasked items gets the masked
+        ids in ascending order at -inf appended).  One device graph build, one eval forward,
+        one masked top-k and one copy of the results back per ``MAX_REQUESTS`` requests (the
+        builder adds its 8-byte size read and a 4-byte status read); a request holds at most
+        64 items (``ServingLimits.max_session_length`` is 50)."""
+        requests = list(requests)
+        if not requests:
+            return []
+        ptr, items, ks = self.validate_batch(requests)
+        out = []
+        for lo in range(0, len(requests), MAX_REQUESTS):
+            hi = min(lo + MAX_REQUESTS, len(requests))
+            out += self._recommend_chunk(ptr[lo: hi + 1] - ptr[lo], items[ptr[lo]: ptr[hi]], ks[lo:hi])
+        return out
+
+    def _recommend_chunk(self, ptr, items, ks) -> list[tuple[list[int], list[float]]]:
+        T = self.num_items
+        sb = self._request_builder.build_packed(ptr, items, check=False)
+        excl_ptr = excl_ids = None
+        if max(ks) > T - 65:  # a request may run out of unmasked items (<= 65 are masked): exact counts
+            excl_ptr = sb.excl_ptr.tolist()
+            excl_ids = sb.excl_ids[: excl_ptr[-1]].tolist()
+            live = [min(k, T - (excl_ptr[b + 1] - excl_ptr[b])) for b, k in enumerate(ks)]
+        else:
+            live = ks
+        k_max = max(live)
+        se = self.model(sb.batch)  # [B, hidden_dim]
+        ids = scores = [[]] * len(ks)
+        if k_max > 0:
+            idx, sc = torch.ops.etpgt.score_topk(se, self.item_embeddings, k_max, sb.excl_ptr, sb.excl_ids)
+            # one copy back: ids (< 2^53) and fp32 scores are both exact in fp64
+            both = torch.cat([idx.double(), sc.double()], dim=1).cpu()
+            ids, scores = both[:, :k_max].long().tolist(), both[:, k_max:].tolist()
+        self._request_builder.check_status()
+        if live is ks and min(ks) == k_max:  # every request takes all k_max columns
+            return list(zip(ids, scores))
+        out = []
+        for b, k in enumerate(ks):
+            i, s = ids[b][: live[b]], scores[b][: live[b]]
+            if k > live[b]:
+                i = i + excl_ids[excl_ptr[b]: excl_ptr[b] + k - live[b]]
+                s = s + [float("-inf")] * (k - live[b])
+            out.append((i, s))
+        return out
 
     def health(self) -> dict:
         return {

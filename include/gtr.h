@@ -40,6 +40,8 @@
  *                     the table per batch, no selection.
  *   gtr_build_batch   dataloader.py:64-202 SessionDataset.__getitem__ + collate_fn on
  *                     the device (+ gtr_edge_hash_build, gtr_session_counts).
+ *   gtr_serve_build   serving/recommender.py:99-117 session subgraphs of a batch of
+ *                     requests on the device (+ gtr_serve_counts).
  *
  * Conventions: plain pointers + sizes, no torch types; every
  * pointer is a device pointer unless marked (host); stream is a hipStream_t;
@@ -746,6 +748,37 @@ int gtr_build_batch_strided(const gtr_sessions* ss, const uint64_t* slots, int64
                             const int32_t* order, int64_t* cursor, int B, int64_t stride, int row_group,
                             uint32_t seed, const gtr_batch* out, int32_t* scratch, int64_t* start, int32_t* status,
                             gtr_stream_t stream);
+
+/* ---- serving: request lists -> batch image (etpgt.data.gpu_batch.GpuRequestBuilder) ----
+ * etpgt/serving/recommender.py:99-117,133-134 for a whole batch of ad-hoc sessions on the
+ * device.  Request b holds the 1..64 items req_items[req_ptr[b] .. req_ptr[b+1]), every id
+ * in [0, T) (the HOST checks both; the kernels only clamp the length).  Its nodes are the
+ * sorted unique ids of ALL its items (no target split); its edges are the stored rows
+ * (item_i, item_j), item_i != item_j, with both ends among the nodes, directed
+ * item_i -> item_j in the orientation stored -- the hash (gtr_edge_hash_build) holds the
+ * keys item_i * T + item_j of those rows and every ordered pair is probed; its exclusion
+ * list for gtr_score_topk_masked is {0} U nodes, ascending.                             */
+typedef struct gtr_requests {
+  const int32_t* req_ptr;   /* [B+1] item offsets                               */
+  const int32_t* req_items; /* items in request order                           */
+  int32_t num_requests;     /* B <= 16384                                       */
+  int32_t num_items;        /* T (table rows)                                   */
+} gtr_requests;
+
+/* counts[3b .. 3b+2] = nodes, edges, excluded ids of request b; totals[0 .. 1] = the
+ * batch's node and edge counts (what the host sizes the image's capacities from).     */
+int gtr_serve_counts(const gtr_requests* rq, const uint64_t* slots, int64_t num_slots, int32_t* counts,
+                     int32_t* totals, gtr_stream_t stream);
+/* The batch image of the requests into *out (n_neg = 0, targets zero; otherwise what
+ * gtr_build_batch writes), excl_ptr [B+1] and excl_ids [excl_cap].  counts: those of
+ * gtr_serve_counts for the same requests and hash.  scratch: [3 * b_cap + 2] int32,
+ * 8-byte aligned.  status [2] as gtr_build_batch: status[0] = 1 (and an empty header,
+ * nothing else written) if the batch exceeds out's capacities or excl_cap; status[1] |=
+ * that code, and |= 4 if a request's counts are not the ones passed (that request is not
+ * written).  row_group = the layer kernels' R for out's n_cap.                         */
+int gtr_serve_build(const gtr_requests* rq, const uint64_t* slots, int64_t num_slots, const int32_t* counts,
+                    int row_group, const gtr_batch* out, int32_t* excl_ptr, int32_t* excl_ids, int64_t excl_cap,
+                    int32_t* scratch, int32_t* status, gtr_stream_t stream);
 
 /* ---- Laplacian positional-encoding precompute (etpgt.encodings.laplacian_gpu) ------
  * Replaces the host eigsh of compute_laplacian_pe (etpgt/encodings/laplacian_pe.py:19-66:
