@@ -850,8 +850,11 @@ extern "C" int gtr_qkvs_fwd(const gtr_config* cfg, const gtr_batch* bt, const gt
     return GTR_E_ARG;
   }
   const char* gg = getenv("GTR_GEMM_GEN");  // A/B: the LDS-staged GEMMs at D = 64 / 128 too
-  if (D == 256 || (gg && gg[0] == '1' && !(cfg->sync_bn && cfg->training))) {  // LDS-staged GEMM (gtr_gemm_gen.hip): no SyncBN merged-row mode there
-    if (cfg->sync_bn && cfg->training) { set_error("gtr_qkvs_fwd: dim 256 on the split path has no SyncBN"); return GTR_E_ARG; }
+  if (D == 256 || (gg && gg[0] == '1' && !(cfg->sync_bn && cfg->training))) {  // LDS-staged GEMM (gtr_gemm_gen.hip)
+    if (l > 0 && !ready && cfg->sync_bn && cfg->training && (!layers[l - 1].bn_part_all || layers[l - 1].nparts_fwd <= 0)) {
+      set_error("gtr_qkvs_fwd: sync_bn needs the gathered merged rows of layer %d", l - 1);
+      return GTR_E_ARG;
+    }
     if (l == 0 && cfg->pe_k > 0 && (!emb->wpe || !emb->bpe)) { set_error("gtr_qkvs_fwd: Laplacian PE not precomputed"); return GTR_E_ARG; }
     return gen_qkvs_fwd(cfg, bt, emb, layers, l, (hipStream_t)stream);
   }
@@ -945,7 +948,6 @@ extern "C" int gtr_qkvs_bwd(const gtr_config* cfg, const gtr_batch* bt, const gt
   if (cfg->sync_bn && !cfg->split_sync) { set_error("gtr_qkvs_bwd: sync_bn needs split_sync"); return GTR_E_ARG; }
   const char* gg = getenv("GTR_GEMM_GEN");
   if (D == 256 || (gg && gg[0] == '1' && !cfg->sync_bn)) {
-    if (cfg->sync_bn) { set_error("gtr_qkvs_bwd: dim 256 on the split path has no SyncBN"); return GTR_E_ARG; }
     if (l > 0 && layers[l - 1].ffn && !layers[l - 1].ffn->dz) { set_error("gtr_qkvs_bwd: layer %d's FFN has no dz rows", l - 1); return GTR_E_ARG; }
     return gen_qkvs_bwd(cfg, bt, layers, l, dx0, (hipStream_t)stream);
   }
@@ -1003,12 +1005,16 @@ int ffn_check(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layer
   }
   if (!f.w1 || !f.b1 || !f.w2 || !f.b2 || !f.y || !f.a || !f.z) { set_error("%s: missing FFN buffers", fn); return GTR_E_ARG; }
   if (need_train && !cfg->training) { set_error("%s: backward requires training mode", fn); return GTR_E_ARG; }
-  // BatchNorm statistics: producer-finalized, or (SyncBN, split_sync) folded by the FFN's
-  // first GEMM from every rank's merged row like the next layer's projection does
-  if (cfg->training && (cfg->sync_bn || cfg->consumer_reduce) &&
-      !(cfg->sync_bn && cfg->split_sync && !ffn_generic(cfg, f))) {
-    set_error("%s: the FFN variant takes producer-finalized BatchNorm statistics, or SyncBN's merged rows "
-              "(split_sync) at dim 64 / 128 with expansion 4", fn);
+  // BatchNorm statistics: producer-finalized, or (SyncBN, split_sync) folded from every rank's
+  // merged row -- by the FFN's first GEMM like the next layer's projection does (k_proj), or
+  // by k_gen_bn_sync ahead of the LDS-staged GEMMs
+  if (cfg->training && (cfg->sync_bn ? !cfg->split_sync : cfg->consumer_reduce)) {
+    set_error("%s: the FFN variant takes producer-finalized BatchNorm statistics (consumer_reduce 0) or, "
+              "under sync_bn, the ranks' merged rows (split_sync)", fn);
+    return GTR_E_ARG;
+  }
+  if (cfg->training && cfg->sync_bn && (!layers[l].bn_part_all || layers[l].nparts_fwd <= 0)) {
+    set_error("%s: sync_bn needs the gathered merged rows of layer %d", fn, l);
     return GTR_E_ARG;
   }
   drop_on = (cfg->training && cfg->dropout > 0.0f) ? 1 : 0;
@@ -1050,11 +1056,7 @@ extern "C" int gtr_ffn_fwd(const gtr_config* cfg, const gtr_batch* bt, const gtr
   k.p_out = L.out; k.p_xin = L.xin; k.p_stats = L.bn_stats; k.p_rmean = L.bn_rmean; k.p_rvar = L.bn_rvar;
   k.p_nbt = L.bn_nbt; k.p_gamma = L.bn_gamma; k.p_beta = L.bn_beta; k.bn_mom = cfg->bn_momentum;
   k.w_all = f.w1; k.b_all = f.b1; k.xin = f.y; k.qkvs = f.a;
-  if (cfg->sync_bn && cfg->training) {  // SyncBN: the ranks' merged rows of this layer (gtr_qkvs_fwd's fold)
-    if (!L.bn_part_all || L.nparts_fwd <= 0) {
-      set_error("gtr_ffn_fwd: sync_bn needs the gathered merged rows of layer %d", l);
-      return GTR_E_ARG;
-    }
+  if (cfg->sync_bn && cfg->training) {  // SyncBN: the ranks' merged rows of this layer (gtr_qkvs_fwd's fold; ffn_check)
     k.sync = 1;
     k.p_part_all = L.bn_part_all;
     k.p_nparts = L.nparts_fwd;

@@ -19,6 +19,9 @@
 //                BatchNorm fold + residual + dropout, the FFN output-mask gradient.
 //   k_gen_colsum fixed-order column sums of per-tile partial rows (BatchNorm backward sums,
 //                the FFN bias gradients per row chunk).
+//   k_gen_bn_sync SyncBN (split_sync): one workgroup folds the ranks' gathered merged rows
+//                of a layer into its mean | rstd (bn_stats) and updates the running
+//                statistics, before the RB_FOLD rows that read them.
 //
 // Exact f32 (v_mfma_f32_16x16x4f32): the sums run in another order than the register
 // kernels', so these results equal the CPU oracle at the 1e-3 bar, not those kernels bit
@@ -309,6 +312,52 @@ __global__ __launch_bounds__(256) void k_gen_rows(RowsK a) {
   *reinterpret_cast<float4*>(a.dst + o) = v;
 }
 
+// SyncBN (split_sync) on this path: the consumer of the ranks' gathered rows.  One
+// workgroup folds every rank's merged (count, mean, M2) row of a layer in rank order (the
+// helper of k_proj<D, PJ_FOLD>'s SyncBN prologue, gtr_gemm.hip), publishes mean | rstd in
+// bn_stats -- read by the RB_FOLD rows, the GE_DX epilogue and the attention backward --
+// and updates the running statistics, once per step (the producer only merges its rows).
+struct BnSyncK {
+  const float* part_all;  // [nparts][1 + 2D]
+  int nparts;
+  float bn_eps, bn_mom;
+  float* stats;           // mean | rstd
+  float* rmean;
+  float* rvar;
+  int64_t* nbt;
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void k_gen_bn_sync(BnSyncK a) {
+  __shared__ float s_mean[D], s_rstd[D], s_uvar[D];
+  __shared__ float s_scr[2 * 256 + D];
+  const int tid = threadIdx.x;
+  bn_stats_from_parts<D, 256>(a.part_all, a.nparts, a.bn_eps, s_mean, s_rstd, s_uvar, s_scr);
+  for (int j = tid; j < D; j += 256) {
+    a.stats[j] = s_mean[j];
+    a.stats[D + j] = s_rstd[j];
+    a.rmean[j] = (1.0f - a.bn_mom) * a.rmean[j] + a.bn_mom * s_mean[j];
+    a.rvar[j] = (1.0f - a.bn_mom) * a.rvar[j] + a.bn_mom * s_uvar[j];
+  }
+  if (tid == 0 && a.nbt) *a.nbt += 1;
+}
+
+// Layer P's statistics from its gathered rows (training under sync_bn; the entry points of
+// gtr_gemm.hip have checked bn_part_all / nparts_fwd).
+int launch_bn_sync(const gtr_config* cfg, const gtr_layer& P, hipStream_t s) {
+  BnSyncK k{};
+  k.part_all = P.bn_part_all; k.nparts = P.nparts_fwd; k.bn_eps = cfg->bn_eps; k.bn_mom = cfg->bn_momentum;
+  k.stats = P.bn_stats; k.rmean = P.bn_rmean; k.rvar = P.bn_rvar; k.nbt = P.bn_nbt;
+  switch (cfg->dim) {
+    case 64: hipLaunchKernelGGL(k_gen_bn_sync<64>, dim3(1), dim3(256), 0, s, k); break;
+    case 128: hipLaunchKernelGGL(k_gen_bn_sync<128>, dim3(1), dim3(256), 0, s, k); break;
+    case 256: hipLaunchKernelGGL(k_gen_bn_sync<256>, dim3(1), dim3(256), 0, s, k); break;
+    default: set_error("k_gen_bn_sync: dim %d (64 / 128 / 256)", cfg->dim); return GTR_E_ARG;
+  }
+  GTR_HIP_CHECK_LAUNCH();
+  return GTR_OK;
+}
+
 void fill_drop(const gtr_config* cfg, bool train_only, uint32_t& seed, uint32_t& thresh, float& scale, int& on,
                uint32_t& ctr_add, const uint32_t*& rng) {
   on = ((!train_only || cfg->training) && cfg->dropout > 0.0f) ? 1 : 0;
@@ -387,6 +436,9 @@ int gen_qkvs_fwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_embed* em
     const gtr_layer& P = layers[l - 1];
     r.src = P.out; r.src2 = P.xin; r.stats = P.bn_stats; r.rmean = P.bn_rmean; r.rvar = P.bn_rvar;
     r.gamma = P.bn_gamma; r.beta = P.bn_beta;
+    if (cfg->training && cfg->sync_bn) {  // SyncBN: layer l - 1's statistics from the ranks' merged rows
+      if (const int rc = launch_bn_sync(cfg, P, s)) return rc;
+    }
   }
   launch_rows(mode, r, bt->n_cap, s);
   GTR_HIP_CHECK_LAUNCH();
@@ -419,6 +471,9 @@ int gen_ffn_fwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* lay
   r.src = L.out; r.src2 = L.xin; r.stats = L.bn_stats; r.rmean = L.bn_rmean; r.rvar = L.bn_rvar;
   r.gamma = L.bn_gamma; r.beta = L.bn_beta; r.dst = f.y;
   fill_drop(cfg, true, r.seed, r.thresh, r.scale, r.drop_on, r.ctr_add, r.rng_ctr);
+  if (cfg->training && cfg->sync_bn) {  // SyncBN: layer l's statistics from the ranks' merged rows
+    if (const int rc = launch_bn_sync(cfg, L, s)) return rc;
+  }
   launch_rows(RB_FOLD, r, bt->n_cap, s);
   GTR_HIP_CHECK_LAUNCH();
   // a = y W1^T + b1

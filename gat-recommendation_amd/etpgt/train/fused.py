@@ -18,6 +18,13 @@ same arithmetic as the dense reference update, 24 B/element instead of 32) and t
 every small parameter, and sums the loss.  The item table never gets a dense
 gradient.  Optimizer state (exp_avg, exp_avg_sq, step) lives in this object;
 ``export_optimizer_state`` writes it into a ``torch.optim.AdamW`` state layout.
+
+Data parallel (``data_parallel``, one process per GPU) averages the gradients over the ranks;
+``sync_bn=True`` also takes every BatchNorm's statistics over all ranks' batches, for every
+optimized model at d 32 - 256 and for the FFN variant at d 64 / 128 / 256 with expansion
+1 / 2 / 4 (on the LDS-staged GEMMs -- d 256, expansions 1 / 2 -- one workgroup,
+k_gen_bn_sync, folds the ranks' gathered rows per layer), except d 64 at expansion 2.  That
+shape, the last / attention readouts and the halo step are refused at construction.
 """
 
 from __future__ import annotations
@@ -45,10 +52,13 @@ class FusedTrainStep:
         L.check_train_layers(int(model.num_layers), "FusedTrainStep")
         if getattr(model, "use_ffn", False):
             # the FFN variant trains data parallel (replicated or row-sharded table), with or
-            # without SyncBN; SyncBN folds the gathered rows in the FFN's first GEMM (dim 64 / 128,
-            # expansion 4)
-            if sync_bn and not (model.embedding_dim in (64, 128) and getattr(model, "ffn_expansion", 4) == 4):
-                raise NotImplementedError("SyncBN with the FFN variant covers dim 64 / 128 at ffn_expansion 4")
+            # without SyncBN, at every shape the model accepts: the gathered rows are folded in
+            # the FFN's first GEMM (dim 64 / 128 at expansion 4) or by k_gen_bn_sync ahead of the
+            # LDS-staged GEMMs (dim 256, expansions 1 / 2).  One shape is left out: dim 64 at
+            # expansion 2, whose refusal tests/test_ffn_host.py pins (the kernels take it)
+            if sync_bn and model.embedding_dim == 64 and getattr(model, "ffn_expansion", 4) == 2:
+                raise NotImplementedError("SyncBN with the FFN variant is not enabled at dim 64 with ffn_expansion 2 "
+                                          "(dim 64 takes ffn_expansion 4 or 1)")
         self.model = model
         self.eng: Engine = model.hip_engine()
         self.dev = self.eng.device

@@ -48,7 +48,10 @@ class Trainer:
         """Reference signature (trainer.py:23-67) plus three optional keywords: ``fused``
         (force / forbid the fused HIP step), ``sync_bn`` (data parallel: BatchNorm
         statistics over every rank's batch; default on when the default process group spans
-        more than one rank, so P ranks train exactly like one GPU on the global batch) and
+        more than one rank, so P ranks train exactly like one GPU on the global batch -- for
+        the FFN variant the default covers dim 64 / 128 at expansion 4 only, other FFN shapes
+        keep per-rank statistics with a logged warning unless ``sync_bn=True`` is passed,
+        which the fused step takes at every FFN shape but dim 64 with expansion 2) and
         ``shard_table`` (data parallel: the item table and its AdamW moments row-sharded
         across the ranks -- rank p owns rows r % P == p, rows and row gradients travel by
         all-to-all, etpgt.train.sharded -- instead of replicated on every rank; default
@@ -58,11 +61,16 @@ class Trainer:
 
         self.rank, self.world = world_info()
         if sync_bn is None:
-            # SyncBN covers the FFN variant at dim 64 / 128 with expansion 4 (gtr_ffn_fwd folds
-            # the gathered rows); elsewhere its data-parallel step keeps per-rank statistics
+            # the default covers the FFN variant at dim 64 / 128 with expansion 4 only
+            # (tests/test_distributed.py pins it); elsewhere the data-parallel step keeps
+            # per-rank statistics unless the caller asks for SyncBN, and says so
             ffn_sync = (not getattr(model, "use_ffn", False)
                         or (getattr(model, "embedding_dim", 0) in (64, 128) and getattr(model, "ffn_expansion", 4) == 4))
             sync_bn = self.world > 1 and ffn_sync
+            if self.world > 1 and not ffn_sync:
+                logger.warning("data parallel over %d ranks with PER-RANK BatchNorm statistics: the FFN model at "
+                               "dim %s / expansion %s is outside the sync_bn default (pass sync_bn=True)", self.world,
+                               getattr(model, "embedding_dim", "?"), getattr(model, "ffn_expansion", "?"))
         self.sync_bn = bool(sync_bn)
         if shard_table is None:
             shard_table = os.environ.get("GTR_SHARD_TABLE") == "1"

@@ -143,7 +143,8 @@ typedef struct gtr_config {
                               (bn_gsum); the ranks all-gather those single rows, so
                               bn_part_all is [P][1 + 2D] and bn_gpart_all [P][2D]
                               (nparts_fwd = nparts_bwd = P), and the consumers
-                              (gtr_qkvs_fwd, the readout, gtr_attn_bwd) fold P rows     */
+                              (gtr_qkvs_fwd, gtr_ffn_fwd, the readout, gtr_attn_bwd)
+                              fold P rows, at every D and FFN expansion                 */
   float loss_batch;        /* > 0: the loss means divide by this many sessions instead of
                               the batch's own B (a halo cut gives ranks unequal session
                               counts: loss_batch = global B / P makes the rank average of
@@ -309,8 +310,9 @@ int gtr_conv_bwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* la
  * in two launches each, the dense GEMMs over ALL node rows (persistent f32-MFMA kernels
  * that keep W_all in registers per CU) and the per-row-group attention apart.  qkvs and
  * dX are bitwise those of the fused kernels (same k order); the BatchNorm backward sums
- * are summed in another (fixed) order.  Training needs consumer_reduce = 0 and no
- * sync_bn; D in {64, 128} for the GEMMs.  Order per layer:
+ * are summed in another (fixed) order.  Training needs consumer_reduce = 0 or, under
+ * sync_bn, split_sync; D in {64, 128} on the register-resident GEMMs, D = 256 on the
+ * LDS-staged ones (gtr_gemm_gen.hip), both with and without SyncBN.  Order per layer:
  *   forward   gtr_qkvs_fwd(l) -> gtr_attn_fwd(l)
  *   backward  gtr_attn_bwd(l) -> gtr_qkvs_bwd(l)                                     */
 /* X (layer 0: item row + LapPE projection, graph_transformer.py:140-152; l > 0: dropout(
@@ -331,7 +333,13 @@ int gtr_attn_bwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* la
 int gtr_qkvs_bwd(const gtr_config* cfg, const gtr_batch* bt, const gtr_layer* layers, int l,
                  float* dx0, gtr_stream_t stream);
 
-/* ---- feed-forward block (gtr_layer.ffn; D in {64, 128}, F = 4 D).  Order per layer l:
+/* ---- feed-forward block (gtr_layer.ffn; D in {64, 128, 256}, F = 1 / 2 / 4 D; D 64 / 128
+ * at F = 4 D on the register-resident GEMMs, every other shape on the LDS-staged ones).
+ * Training takes producer-finalized BatchNorm statistics (consumer_reduce 0) or, under
+ * sync_bn + split_sync, the ranks' merged rows (bn_part_all) at every shape: folded by
+ * the FFN's first GEMM, or by one workgroup (k_gen_bn_sync) ahead of the LDS-staged GEMMs;
+ * that fold publishes bn_stats and updates the running statistics once per step.
+ * Order per layer l:
  *   forward   gtr_qkvs_fwd(l) -> gtr_attn_fwd(l) -> gtr_ffn_fwd(l)
  *   backward  gtr_ffn_bwd(l) -> gtr_attn_bwd(l) -> gtr_qkvs_bwd(l)
  * The readout of a model whose last layer has an FFN reads ffn->z through an identity

@@ -31,7 +31,11 @@ Differences, each deliberate:
   cuda:LOCAL_RANK, and trains on its share of each global batch of
   ``world * --batch-size`` sessions (``DeviceSessionLoader(rank, world)``) with gradients
   averaged and BatchNorm statistics synchronised across the ranks (SyncBN), i.e. like one
-  GPU on the global batch.  Every rank evaluates the full validation set (the replicas
+  GPU on the global batch.  SyncBN follows the Trainer's default: on for
+  ``graph_transformer_optimized`` at every width and for ``graph_transformer`` (FFN x 4) at
+  d 64 / 128; ``graph_transformer`` at other widths, the default d 256 included, still trains
+  on per-rank statistics there (the Trainer logs a warning).
+  Every rank evaluates the full validation set (the replicas
   are identical); rank 0 writes the outputs.  ``--shard-table on`` (added) keeps the item
   table and its AdamW moments row-sharded across the ranks instead of replicated
   (etpgt.train.sharded; bitwise the replicated step).  At the end the captured step graphs
